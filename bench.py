@@ -15,7 +15,12 @@ Workloads (`--config`):
 
 A "step" is one pass of the hot path over one batch of synthetic PCM per stream, already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds everything else the line can carry:
+the `secondary` configurations (cfg3 / cfg4 / the other one of cfg2 / cfg5, the reference's default shapes, waveform, streaming
+cadence, oscilloscope rates), the CPU `cpu_baseline` and, at N > 1, the run's own N = 1 leg of the same workload.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float32 / float64; see dump_outputs).
 
 N > 1: the driver launches `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` (RANK / WORLD_SIZE in
 the environment).  Started WITHOUT those (`python bench.py --gpus 8`), this process spawns exactly that launcher as a child —
@@ -66,7 +71,14 @@ def parse_args(argv=None):
                          "ranks meet; the line then carries n1_same_workload.measured)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / gather check without device work (CPU tests: OMX_BENCH_BACKEND=gloo)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary configurations, the CPU baseline and (N > 1) the N = 1 leg; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (rank 0's shard at N > 1)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------ launcher
@@ -195,6 +207,81 @@ def cpu_baseline(columns, log):
                       f"single_thread = 1 stream x {columns} columns"}
 
 
+# ------------------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ARRAY_BYTES = 7 << 20   # per array; a workload dumps at most 7 arrays (+ the row indices of the sampled ones): under 64 MB
+
+
+def dump_outputs(out_dir, torch, device, update, n_streams, log):
+    """What the timed path handed its caller in the last timed step — the capture-group update (omx_capture_group_update: device
+    buffers of every enabled visual, valid until the next ingest) — as DIR/<name>.npy, float32 where the library writes f32 and float64
+    for its integer outputs.  An array larger than DUMP_ARRAY_BYTES is represented by a fixed sample of its rows (seeded by the array's
+    name: the same rows whenever the shapes are the same), and DIR/<name>_rows.npy holds the indices of the rows taken."""
+    import zlib
+    from openmeters_amd import capi
+    from openmeters_amd.sharding import STATS_COLUMNS
+    os.makedirs(out_dir, exist_ok=True)
+    S = n_streams
+    written = {}
+
+    def view(ptr, shape, typestr):
+        t = torch.as_tensor(DeviceView(ptr, shape, typestr), device=device)
+        return t if typestr == "<f4" else t.to(torch.float64)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = arr.nbytes
+
+    def save_rows(name, t, transform=None):
+        """t: device tensor [R, ...], float32 or float64; every row, or a seeded sample of them when t is larger than DUMP_ARRAY_BYTES"""
+        idx = None
+        if t.numel() * t.element_size() > DUMP_ARRAY_BYTES:
+            k = max(1, DUMP_ARRAY_BYTES // (t[0].numel() * t.element_size()))
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.shape[0], size=k, replace=False))
+            t = t.index_select(0, torch.as_tensor(idx, device=device))
+        arr = t.cpu().numpy()
+        save(name, transform(arr, idx) if transform else arr)
+        if idx is not None:
+            save(name + "_rows", idx.astype(np.float64))
+
+    if update.produced & capi.VISUAL_SPECTROGRAM:
+        sg = update.spectrogram
+        cols, stride = int(sg.n_columns), int(sg.column_stride)
+        assert sg.kind == 0 and sg.d_points, "the bench workloads are reassigned spectrograms"
+        counts = view(sg.d_counts, (S, cols), "<i4")
+        save_rows("spectrogram_counts", counts)
+
+        def valid_points(arr, idx):   # (time_offset, freq_hz, power) per point; the slots past a column's count are not output: zeroed
+            n = counts.reshape(-1).cpu().numpy()[idx if idx is not None else slice(None)]
+            arr = arr.reshape(len(arr), stride, 3)
+            arr[np.arange(stride)[None, :] >= n[:, None]] = 0.0
+            return arr
+        # rows: stream * n_columns + column
+        save_rows("spectrogram_points", view(sg.d_points, (S * cols, stride * 3), "<f4"), valid_points)
+    if update.produced & capi.VISUAL_SPECTRUM:
+        sp = update.spectrum
+        hops, bins = int(sp.n_hops_out), int(sp.bins)
+        save_rows("spectrum_traces", view(sp.d_traces, (S * hops, 2, 2, bins), "<f4"))   # rows: stream * n_hops_out + hop
+        save_rows("spectrum_frequency_bins", view(sp.d_frequency_bins, (bins,), "<f4"))
+    if update.produced & capi.VISUAL_LOUDNESS and update.d_loudness:
+        blocks = int(update.n_blocks)
+        words = C.sizeof(capi.CLoudnessSnapshot) // 4
+        floats = capi.CLoudnessSnapshot.channel_count.offset // 4   # short-term, momentary, then rms fast / rms slow / true peak x 8 channels
+        snaps = view(update.d_loudness, (S, blocks, words), "<f4")[:, :, :floats]
+        save_rows("loudness_snapshots", snaps)
+    if update.produced & capi.VISUAL_STEREOMETER:
+        st = update.stereometer
+        blocks, target = int(st.n_blocks), int(st.target)
+        save_rows("stereometer_correlations", view(st.d_correlations, (S, blocks, 4), "<f4"))
+        save_rows("stereometer_produced", view(st.d_produced, (S, blocks), "<i4"))
+        if st.d_points:
+            save_rows("stereometer_points", view(st.d_points, (S, 4, target, 2), "<f4"))
+    if update.d_stats_rows:
+        save_rows("stats_rows", view(update.d_stats_rows, (S, len(STATS_COLUMNS)), "<f4"))
+    total = sum(written.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    log(f"dump-outputs: {len(written)} arrays, {total / 1e6:.1f} MB in {out_dir}")
+
+
 # ------------------------------------------------------------------------------------------------------------ rank body
 def main():
     args = parse_args()
@@ -242,11 +329,11 @@ def main():
                               "config": {"workload": config, "streams_per_gpu": S, "gathered_rows": int(table.shape[0])}}), flush=True)
         return
 
-    # N > 1: the same per-GPU workload at N = 1, measured by THIS run (rank 0, as a child process that is gone before this process
-    # touches the GPU; the other ranks wait in the rendezvous meanwhile) so that weak-scaling efficiency is read against a number of
-    # the same box, clocks and build
+    # N > 1, --full: the same per-GPU workload at N = 1, measured by THIS run (rank 0, as a child process that is gone before this
+    # process touches the GPU; the other ranks wait in the rendezvous meanwhile) so that weak-scaling efficiency is read against a
+    # number of the same box, clocks and build
     n1_measured = None
-    if world > 1 and rank == 0 and not args.no_n1:
+    if world > 1 and rank == 0 and args.full and not args.no_n1:
         env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "GROUP_RANK", "ROLE_RANK", "LOCAL_WORLD_SIZE",
                                                                 "MASTER_ADDR", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", config, "--steps", str(args.steps), "--warmup", str(args.warmup),
@@ -334,7 +421,7 @@ def main():
                     stats[:, 9] = cf[:, -1]
                     return stats
                 gather_on_side(rows, [counts])
-            return up
+            return g
     else:
         pipe = FullPipeline(api, S)
         group = pipe.group
@@ -347,14 +434,15 @@ def main():
             if up is not None and world > 1:
                 snapshot = rows.clone()   # (the library reuses its row buffer in the next ingest)
                 gather_on_side(lambda: snapshot, [snapshot])
-            return up
+            return g
 
     # BASELINE.json's other single-GPU configurations (a few seconds; never part of `value`): cfg3 loudness, cfg4 oscilloscope +
     # stereometer, the other one of cfg2 / cfg5, the waveform bank, the streaming cadence.  Measured AHEAD of the timed region since round 6:
     # behind it, a `--steps 20` run (36 ms) was timed on a chip still ramping its clocks — 36.4 M frames/s where the same box gives 37.8 M
     # over 200 steps ("make 20 steps robust"); `step_ms_spread` still shows every step of the timed region.
+    # --full only: 20-step lines measured without them stay within 0.5 % of the lines measured behind them (same box, 4 runs each).
     secondary_result = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         try:
             import bench_meters
             import bench_pipeline
@@ -381,13 +469,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    last = None
+    g = None
     # one event per step boundary on the step's stream (no synchronisation: the spread of the steps inside the timed region, read back
     # after it — a 20-step run is a 40 ms sample of a clock that moves +-15 % box to box)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     marks[0].record()
     for i in range(args.steps):
-        last = step()
+        g = step()
         marks[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -403,9 +491,12 @@ def main():
     step_spread = {"min": step_ms[0], "median": step_ms[len(step_ms) // 2], "p95": step_ms[min(len(step_ms) - 1, int(0.95 * len(step_ms)))],
                    "max": step_ms[-1], "unit": "ms", "note": "device time between consecutive step boundaries on the step's stream (HIP events)"}
     kernel_ms, launches = group.kernel_time()
+    last = g.spectrogram if g.produced & capi.VISUAL_SPECTROGRAM else None
     assert last is not None and last.n_columns == cols_per_step, (last.n_columns if last else None, cols_per_step)
     counts = torch.as_tensor(DeviceView(last.d_counts, (S, last.n_columns), "<i4"), device=device)
     mean_points = float(counts.to(torch.float64).mean().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch, device, g, S, log)
 
     frames_total = world * S * cols_per_step * args.steps
     value = frames_total / elapsed
@@ -515,7 +606,7 @@ def main():
     if rank == 0:
         if secondary_result is not None:
             result["secondary"] = secondary_result
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args.cpu_columns, log)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -127,8 +127,8 @@ def test_cfg5_full_shard_1024_streams_replication_shift_partition_and_oracle_row
 
 def test_bench_two_ranks_on_one_gpu_over_gloo_runs_the_cfg5_step():
     """`python bench.py --gpus 2` (no RANK in the environment) on a 1-GPU box: the launcher starts two ranks, both run the
-    cfg5 step (full pipeline, small shard) on device 0, the summary rows travel over gloo; one JSON line, n_gpus = 2, and
-    `python bench.py --config cfg5` at N = 1 runs the same step."""
+    cfg5 step (full pipeline, small shard) on device 0, the summary rows travel over gloo; one JSON line, n_gpus = 2 (with --full:
+    the run's own N = 1 leg), and `python bench.py --config cfg5` at N = 1 runs the same step."""
     import json
     import os
     import subprocess
@@ -137,7 +137,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo_runs_the_cfg5_step():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(OMX_BENCH_BACKEND="gloo", OMP_NUM_THREADS="1")
     common = ["--steps", "3", "--warmup", "2", "--streams", "16", "--no-secondary", "--no-cpu-baseline"]
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2"] + common, env=env, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full"] + common, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -151,6 +151,45 @@ def test_bench_two_ranks_on_one_gpu_over_gloo_runs_the_cfg5_step():
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     one = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert one["n_gpus"] == 1 and one["config"]["name"] == "cfg5" and one["roofline"]["mean_points_per_frame"] > 1900
+
+
+def test_bench_plain_run_dumps_the_outputs_of_its_last_step(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the headline line alone (no secondary configurations, no CPU baseline),
+    `--steps` timed steps, and the last step's outputs as float32 / float64 .npy files, 64 MB at most; a second run with the same
+    arguments writes the same arrays bit for bit (same synthetic inputs, deterministic kernels).  cfg5 dumps every bank of its group."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def run(out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--streams", "8",
+                            "--frames-per-step", "16384", "--dump-outputs", str(out)] + list(extra), env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "secondary" not in line and "cpu_baseline" not in line
+        arrays = {f[:-4]: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+        assert all(f.endswith(".npy") for f in os.listdir(out))
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) <= 64 << 20
+        return line, arrays
+
+    line, first = run(tmp_path / "a")
+    assert line["config"]["name"] == "cfg2"
+    assert {"spectrogram_counts", "spectrogram_points", "spectrum_traces", "spectrum_frequency_bins"} <= set(first)
+    assert first["spectrogram_counts"].shape == (8, 64) and first["spectrogram_counts"].min() > 0
+    _, second = run(tmp_path / "b")
+    assert set(first) == set(second)
+    for name in first:
+        assert np.array_equal(first[name], second[name]), name
+    _, cfg5 = run(tmp_path / "c", "--config", "cfg5")
+    assert {"spectrogram_counts", "spectrogram_points", "loudness_snapshots", "stereometer_correlations", "stereometer_produced",
+            "stereometer_points", "stats_rows"} <= set(cfg5)
+    assert cfg5["stats_rows"].shape == (8, 12) and np.isfinite(cfg5["loudness_snapshots"]).any()
 
 
 def test_capture_group_equals_separate_banks_plus_torch_rows(omx):

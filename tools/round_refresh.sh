@@ -11,7 +11,10 @@ cp gpurun_out/${TAG}_meters/meters_traffic.json profiles/${TAG}_meters_traffic.j
 # (the records bench.py echoes into roofline.traffic were the ones left behind, twice)
 cp gpurun_out/$TAG/traffic.json gpurun_out/${TAG}_traffic.json
 cp gpurun_out/${TAG}_meters/meters_traffic.json gpurun_out/${TAG}_meters_traffic.json
-python bench.py > gpurun_out/${TAG}_bench_line.json 2> gpurun_out/${TAG}_bench_line.log
+# the default line with everything it can carry (secondary configurations, cpu_baseline), beside the traffic records: in the folder
+# tools/profile_bench.sh left <tag>/ in, which is where tools/collect_round.sh looks for all three
+RECORDS=$(dirname "$(ls -d -- */"$TAG"/ | head -n 1)")
+python bench.py --full > "$RECORDS/${TAG}_bench_line.json" 2> "$RECORDS/${TAG}_bench_line.log"
 python bench.py --config cfg5 --no-cpu-baseline --no-secondary > gpurun_out/${TAG}_bench_line_cfg5.json 2> gpurun_out/${TAG}_bench_line_cfg5.log
 {
 echo "== tools/bench_sizes.py =="; python tools/bench_sizes.py 2>&1 | grep -v amdgpu.ids
