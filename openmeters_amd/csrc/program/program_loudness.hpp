@@ -1,0 +1,106 @@
+// ProgramLoudnessBank: the EBU R 128 programme figures (gated integrated loudness, loudness range, maxima) for S streams.
+// include/omx/program_loudness.h states the definitions; program_loudness_kernels.hip holds the kernels.
+// Self-contained: shares no state and no kernel with LoudnessBank (its copy of the K-weighting step is a later consolidation).
+#pragma once
+#include "../common.hpp"
+#include "../../../include/omx/program_loudness.h"
+
+namespace omx {
+
+constexpr uint32_t kPlTile = 32;          // frames per LDS tile of the segment pass
+constexpr uint32_t kPlChunkFrames = 1024;  // frames per work item of the time-parallel form (never more than one segment)
+constexpr uint32_t kPlSlots = OMX_MAX_CHANNELS;  // state is laid out [stream][8 channel slots] whatever the channel count
+
+// What one call does to one stream: made on the host (every count of a stream follows from the call arguments), uploaded per call.
+struct PlStreamCall {
+    uint32_t frames;    // frames taken in this call (after the capacity clamp)
+    uint32_t phase;     // frames already in the open segment when the call starts
+    uint32_t n_new;     // segments that complete in this call
+    uint32_t reset;     // state cleared before the samples are taken
+    uint64_t seg_base;  // segments stored before the call
+};
+struct PlStreamMeta {  // the host's counters of a stream, for the result pass
+    uint64_t frames;
+    uint32_t segments, overflow;
+};
+
+struct PlArgs {
+    const float* pcm;  // [n_streams][frames_capacity][channels]
+    uint64_t frames_capacity;
+    uint32_t n_streams, channels, slot_shift;  // lane = (stream << slot_shift) + channel
+    uint32_t seg;       // frames per segment
+    uint32_t chunk;     // frames per work item: the whole call (reference order) or kPlChunkFrames (time-parallel, <= seg)
+    uint32_t n_chunks;  // work items per stream
+    uint32_t max_new;   // row length of chan_sums
+    double b[5], a[5];
+    double weights[OMX_MAX_CHANNELS];
+    const PlStreamCall* calls;  // [n_streams]
+    double* state;      // [n_streams][8][4] K-weighting TDF-II state
+    double* starts;     // [n_streams][8][n_chunks][4] start state of every work item (reference order: `state` itself)
+    double* part;       // [n_streams][8] weighted energy sum of the open segment
+    double* chan_sums;  // [n_streams][8][max_new] weighted energy sums of the segments completed in this call
+    double* partials;   // time-parallel: [n_streams][8][n_chunks][2] sums before / after the segment boundary inside a work item
+    const double* zs_weights;   // [chunk][4]: weight of sample k of a work item on its zero-state end state
+    const double* transition;   // [2][4][4]: zero-input transition over `chunk` frames, high parts then low parts
+    double* segments;   // [n_streams][capacity] stored segment energies
+    uint64_t capacity;
+};
+void launch_pl_reset(const PlArgs& a, float* tp_max, float floor_db, hipStream_t stream);
+void launch_pl_reference_order(const PlArgs& a, hipStream_t stream);
+void launch_pl_time_parallel(const PlArgs& a, hipStream_t stream);
+void launch_pl_commit(const PlArgs& a, hipStream_t stream);
+
+struct PlResultArgs {
+    const double* segments;
+    uint64_t capacity;
+    const PlStreamMeta* meta;
+    const float* tp_max;
+    omx_program_loudness_record* records;
+    uint32_t n_streams;
+    float floor_db;
+    double absolute_gate;  // energy of -70 LUFS
+};
+void launch_pl_results(const PlResultArgs& a, hipStream_t stream);
+void launch_pl_true_peak_fold(const omx_loudness_snapshot* snapshots, uint64_t n_blocks, const uint32_t* d_n_blocks, uint32_t n_streams,
+                              float* tp_max, hipStream_t stream);
+
+class ProgramLoudnessBank {
+public:
+    ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_t n_streams, uint32_t capacity_seconds);
+    int reset(const uint8_t* reset_mask);
+    int process(const float* d_pcm, uint64_t frames_capacity, const uint32_t* frames, const uint8_t* reset_mask, uint32_t channels,
+                float sample_rate, const uint8_t positions[OMX_MAX_CHANNELS], hipStream_t stream);
+    int note_snapshots(const omx_loudness_snapshot* d_snapshots, uint64_t n_blocks, const uint32_t* d_n_blocks, hipStream_t stream);
+    int results(hipStream_t stream, const omx_program_loudness_record** d_records);
+    int fetch(uint64_t stream_index, omx_program_loudness_record* dst);
+    int fetch_segments(uint64_t stream_index, uint64_t first, uint64_t count, double* dst);
+    void form(int f) { form_ = f; }
+    int last_form() const { return last_form_; }
+
+private:
+    void set_rate(float rate);
+    void host_tables(hipStream_t stream);
+
+    omx_loudness_config cfg_{};
+    uint32_t n_streams_;
+    uint64_t capacity_;     // segments per stream
+    float rate_ = 0.0f;     // sanitised rate of the running programmes (0: none yet)
+    uint32_t channels_ = 0;
+    uint32_t seg_ = 0;
+    double b_[5], a_[5];
+    std::vector<PlStreamMeta> h_meta_;
+    std::vector<PlStreamCall> h_calls_;
+    DeviceBuffer<double> state_, part_, segments_, chan_sums_, partials_, starts_, zs_weights_, transition_;
+    DeviceBuffer<float> tp_max_;
+    DeviceBuffer<PlStreamCall> calls_;
+    DeviceBuffer<PlStreamMeta> meta_;
+    DeviceBuffer<omx_program_loudness_record> records_;
+    BlobStaging call_staging_, meta_staging_;
+    float tables_rate_ = 0.0f;
+    uint32_t tables_chunk_ = 0;
+    bool dirty_ = true;
+    int form_ = 0, last_form_ = 0;
+    hipStream_t last_stream_ = nullptr;
+};
+
+}  // namespace omx

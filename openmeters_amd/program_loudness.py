@@ -1,0 +1,145 @@
+"""Programme loudness bank (include/omx/program_loudness.h): gated integrated loudness (BS.1770-4), loudness range
+(EBU Tech 3342) and the maxima of momentary loudness, short-term loudness and true peak for S streams on one GPU.
+Inputs are device pointers; nothing here touches sample data."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import capi
+from .capi import Api
+
+_u8x8 = C.c_uint8 * 8
+
+_ENERGIES = ("integrated_energy", "relative_threshold_energy", "lra_low_energy", "lra_high_energy", "momentary_energy",
+             "short_term_energy", "max_momentary_energy", "max_short_term_energy")
+_COUNTS = ("frames", "segments", "gating_blocks", "gating_above_absolute", "gating_above_relative", "short_term_blocks",
+           "short_term_above_absolute", "short_term_above_relative")
+_LEVELS = ("integrated_lufs", "relative_threshold_lufs", "loudness_range_lu", "momentary_lufs", "short_term_lufs",
+           "max_momentary_lufs", "max_short_term_lufs", "max_true_peak_db")
+
+
+class CProgramLoudnessRecord(C.Structure):
+    _fields_ = ([(n, C.c_double) for n in _ENERGIES] + [(n, C.c_uint64) for n in _COUNTS] + [(n, C.c_float) for n in _LEVELS]
+                + [("overflow", C.c_uint32), ("_pad", C.c_uint32)])
+
+
+@dataclass
+class ProgramLoudnessRecord:
+    """omx_program_loudness_record: dB fields floored at the configured floor, the f64 energies they were made from, counts."""
+    integrated_energy: float
+    relative_threshold_energy: float
+    lra_low_energy: float
+    lra_high_energy: float
+    momentary_energy: float
+    short_term_energy: float
+    max_momentary_energy: float
+    max_short_term_energy: float
+    frames: int
+    segments: int
+    gating_blocks: int
+    gating_above_absolute: int
+    gating_above_relative: int
+    short_term_blocks: int
+    short_term_above_absolute: int
+    short_term_above_relative: int
+    integrated_lufs: float
+    relative_threshold_lufs: float
+    loudness_range_lu: float
+    momentary_lufs: float
+    short_term_lufs: float
+    max_momentary_lufs: float
+    max_short_term_lufs: float
+    max_true_peak_db: float
+    overflow: bool
+
+    LEVEL_FIELDS = _LEVELS
+    COUNT_FIELDS = _COUNTS
+    ENERGY_FIELDS = _ENERGIES
+
+
+FORM_BY_SHAPE, FORM_REFERENCE_ORDER, FORM_TIME_PARALLEL = 0, 1, 2
+
+
+class ProgramLoudnessBank:
+    """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
+
+    def __init__(self, api: Api, config: capi.LoudnessConfig, n_streams: int, channels: int = 2, capacity_seconds: int = 3600):
+        self.api = api
+        self.n_streams = n_streams
+        self._h = C.c_void_p()
+        c = config.to_c()
+        api.check(api.fn("program_loudness_bank_create", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)])(
+            C.byref(c), n_streams, channels, capacity_seconds, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.api.fn("program_loudness_bank_destroy", None, [C.c_void_p])(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _per_stream(self, values, dtype, what):
+        if values is None:
+            return None
+        arr = np.ascontiguousarray(values, dtype).reshape(-1)
+        if arr.size != self.n_streams:
+            raise ValueError(f"{what}: {arr.size} entries for a bank of {self.n_streams} streams")
+        return arr
+
+    def reset(self, reset_mask: Optional[Sequence[int]] = None):
+        """R 128 start / reset of the flagged streams (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def set_option(self, option: int, value: int):
+        self.api.check(self.api.fn("program_loudness_bank_set_option", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64])(self._h, option, value))
+
+    def last_form(self) -> int:
+        """1 = the last call ran the reference-order segment pass, 2 = the time-parallel one."""
+        return self.api.fn("debug_program_loudness_bank_last_form", C.c_int, [C.c_void_p])(self._h)
+
+    def process(self, device_ptr: int, frames_capacity: int, channels: int, sample_rate: float, positions: Sequence[int],
+                frames: Optional[Sequence[int]] = None, reset_mask: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        fr = self._per_stream(frames, np.uint32, "frames")
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        f = self.api.fn("program_loudness_bank_process", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, _u8x8, C.c_void_p])
+        return self.api.check(f(self._h, C.c_void_p(device_ptr), frames_capacity, fr.ctypes.data if fr is not None else None,
+                                mask.ctypes.data if mask is not None else None, channels, sample_rate, _u8x8(*positions),
+                                C.c_void_p(stream or 0)))
+
+    def note_snapshots(self, d_snapshots: int, n_blocks: int, d_n_blocks: int = 0, stream: int = 0):
+        """Fold the true peaks of the snapshots a LoudnessBank call left on the device ([n_streams][n_blocks]) into the running maxima."""
+        self.api.check(self.api.fn("program_loudness_bank_note_snapshots", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p])(
+            self._h, C.c_void_p(d_snapshots), n_blocks, C.c_void_p(d_n_blocks or 0), C.c_void_p(stream or 0)))
+
+    def results(self, stream: int = 0) -> int:
+        """Run the result pass on `stream`; returns the device pointer to omx_program_loudness_record[n_streams]."""
+        out = C.c_void_p()
+        self.api.check(self.api.fn("program_loudness_bank_results", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])(
+            self._h, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value
+
+    def fetch(self, stream_index: int) -> ProgramLoudnessRecord:
+        r = CProgramLoudnessRecord()
+        self.api.check(self.api.fn("program_loudness_bank_fetch", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, C.byref(r)))
+        return ProgramLoudnessRecord(*[getattr(r, n) for n in _ENERGIES + _COUNTS + _LEVELS], bool(r.overflow))
+
+    def fetch_segments(self, stream_index: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Stored segment energies e[first : first + count] of one stream (count None: up to the last stored one)."""
+        if count is None:
+            count = self.fetch(stream_index).segments - first
+        out = np.zeros((max(count, 0),), np.float64)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_segments", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, first, count, out.ctypes.data))
+        return out
