@@ -72,8 +72,12 @@ int omx_program_loudness_bank_reset(omx_program_loudness_bank* b, const uint8_t*
 /* d_pcm: device f32 [n_streams][frames_capacity][channels].  frames: host array [n_streams] of per-stream frame counts
  * (<= frames_capacity, 0 allowed), NULL = frames_capacity for every stream.  reset_mask: host array or NULL; flagged streams are
  * reset before their samples are taken.  A rate or channel count other than the one the running programmes started with is refused
- * with OMX_ERR_INVALID unless every stream that has taken samples is reset in the same call.  Rates below 1 kHz: OMX_ERR_UNSUPPORTED.
- * Returns OMX_PRODUCED when any stream took a frame, else OMX_NONE. */
+ * with OMX_ERR_INVALID unless every stream that has taken samples is reset in the same call.
+ * channels is the stride of d_pcm and must be 1 .. OMX_MAX_CHANNELS: anything else is OMX_ERR_INVALID (no clamping).
+ * Rates (after sanitising: at most 768 kHz) below 3364 Hz: OMX_ERR_UNSUPPORTED.  The K-weighting shelf sits at 1681.97 Hz, and up to
+ * twice that the filter has poles outside the unit circle; 3364 Hz is the first whole rate from which every rate is stable.
+ * Also OMX_ERR_INVALID: frames[s] > frames_capacity, frames_capacity > 2^32 - 1, a null d_pcm when any stream brings frames.
+ * A refused call changes nothing.  Returns OMX_PRODUCED when any stream took a frame, else OMX_NONE. */
 int omx_program_loudness_bank_process(omx_program_loudness_bank* b, const float* d_pcm, uint64_t frames_capacity,
                                       const uint32_t* frames, const uint8_t* reset_mask, uint32_t channels, float sample_rate,
                                       const uint8_t positions[OMX_MAX_CHANNELS], void* stream);
@@ -90,7 +94,9 @@ int omx_program_loudness_bank_fetch(omx_program_loudness_bank* b, uint64_t strea
 int omx_program_loudness_bank_fetch_segments(omx_program_loudness_bank* b, uint64_t stream_index, uint64_t first, uint64_t count,
                                              double* dst);
 /* OMX_OPT_KERNEL_FORM: 0 = by call shape (default), 1 = reference-order segment pass (bit-identical segment energies however the
- * programme is cut into calls), 2 = time-parallel segment pass.  Other options / values: OMX_ERR_INVALID. */
+ * programme is cut into calls), 2 = time-parallel segment pass.  Other options / values: OMX_ERR_INVALID.
+ * The time-parallel pass holds 1e-4 dB against the reference order up to 384 kHz.  Above that rate the bank runs the reference-order
+ * pass whatever form is set, 2 included, and omx_debug_program_loudness_bank_last_form reports 1: it never returns looser numbers. */
 int omx_program_loudness_bank_set_option(omx_program_loudness_bank* b, uint32_t option, uint64_t value);
 /* 1 = the last process call ran the reference-order pass, 2 = the time-parallel one, 0 = none yet */
 int omx_debug_program_loudness_bank_last_form(const omx_program_loudness_bank* b);

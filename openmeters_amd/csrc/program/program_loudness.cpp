@@ -122,9 +122,13 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         set_last_error("program loudness process: frames_capacity beyond 2^32 - 1");
         return OMX_ERR_INVALID;
     }
-    const uint32_t channels = std::min<uint32_t>(std::max<uint32_t>(channels_in, 1), OMX_MAX_CHANNELS);
+    if (channels_in == 0 || channels_in > OMX_MAX_CHANNELS) {  // (a clamped count with the caller's stride would read the wrong samples)
+        set_last_error("program loudness process: channels outside 1 .. 8");
+        return OMX_ERR_INVALID;
+    }
+    const uint32_t channels = channels_in;
     const float rate = sanitize_sample_rate(sample_rate);
-    if (rate < 1000.0f) unsupported("programme loudness below 1 kHz");
+    if (rate < kPlMinRate) unsupported("programme loudness below 3364 Hz: the K-weighting filter has poles outside the unit circle");
     bool any = false, any_reset = false;
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const uint64_t f = frames ? frames[s] : frames_capacity;
@@ -207,7 +211,9 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
     const uint32_t item = std::min(kPlChunkFrames, seg_);
     const uint64_t waves = ((uint64_t)n_streams_ << a.slot_shift) / 64 + 1;
     const bool by_shape = max_frames >= 4 * item && waves * 4 < 2048;
-    const bool time_parallel = form_ == 2 || (form_ == 0 && by_shape);
+    // above kPlTimeParallelMaxRate the time-parallel pass cannot hold the parity bar (program_loudness.hpp): the reference order runs,
+    // also for a pinned form 2, and last_form() says so
+    const bool time_parallel = rate_ <= kPlTimeParallelMaxRate && (form_ == 2 || (form_ == 0 && by_shape));
     if (time_parallel) {
         host_tables(stream);
         a.chunk = item;

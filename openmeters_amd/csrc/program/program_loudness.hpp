@@ -10,6 +10,15 @@ namespace omx {
 constexpr uint32_t kPlTile = 32;          // frames per LDS tile of the segment pass
 constexpr uint32_t kPlChunkFrames = 1024;  // frames per work item of the time-parallel form (never more than one segment)
 constexpr uint32_t kPlSlots = OMX_MAX_CHANNELS;  // state is laid out [stream][8 channel slots] whatever the channel count
+// Lowest rate: the K-weighting shelf sits at 1681.97 Hz and its bilinear transform has poles outside the unit circle for every rate
+// from there to twice that (3363.95 Hz; largest pole radius 1.98 at 2 kHz, 1.0006 at 3363 Hz, 0.99997 at 3364 Hz:
+// tests/test_cpu_program_loudness_inputs.py); below 1682 Hz the shelf lies above the rate itself
+constexpr float kPlMinRate = 3364.0f;
+// Highest rate of the time-parallel form.  A work item starts from a state rounded to f64, and the zero-input response amplifies that
+// rounding by up to |A^L| before the poles let it decay: 2.1e6 at 384 kHz, 1.1e7 at 768 kHz (L = 1024).  A CPU model of the form with an
+// exact scan leaves 5e-6 dB on a 5 Hz sine at 0.5 under noise at -60 dBFS at 384 kHz and 8e-5 dB at 768 kHz, against a bar of 1e-4 dB:
+// above 384 kHz the reference order runs whatever form is asked for.
+constexpr float kPlTimeParallelMaxRate = 384000.0f;
 
 // What one call does to one stream: made on the host (every count of a stream follows from the call arguments), uploaded per call.
 struct PlStreamCall {
