@@ -201,6 +201,7 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
     a.capacity = capacity_;
     if (any_reset) launch_pl_reset(a, tp_max_.ptr, cfg_.floor_db, stream);
     if (!taken) {
+        if (peaks_on_ && any_reset) measure_peaks(d_pcm, frames_capacity, 0, stream);  // (the flagged streams' peaks are cleared by the fold)
         OMX_HIP(hipGetLastError());
         return OMX_NONE;
     }
@@ -235,6 +236,7 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         last_form_ = 1;
     }
     launch_pl_commit(a, stream);
+    if (peaks_on_) measure_peaks(d_pcm, frames_capacity, max_frames, stream);
     OMX_HIP(hipGetLastError());
     return OMX_PRODUCED;
 }
@@ -257,6 +259,7 @@ int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_
     r.capacity = capacity_;
     r.meta = meta_.ptr;
     r.tp_max = tp_max_.ptr;
+    r.peaks = peaks_on_ ? peak_records_.ptr : nullptr;
     r.records = records_.ptr;
     r.n_streams = n_streams_;
     r.floor_db = cfg_.floor_db;
@@ -292,11 +295,6 @@ int ProgramLoudnessBank::fetch_segments(uint64_t stream_index, uint64_t first, u
 
 // ---------------------------------------------------------------- C ABI (include/omx/program_loudness.h)
 using namespace omx;
-
-struct omx_program_loudness_bank {
-    ProgramLoudnessBank impl;
-    omx_program_loudness_bank(const omx_loudness_config& c, uint32_t n, uint32_t cap) : impl(c, n, cap) {}
-};
 
 extern "C" {
 

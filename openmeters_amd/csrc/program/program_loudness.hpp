@@ -4,6 +4,7 @@
 #pragma once
 #include "../common.hpp"
 #include "../../../include/omx/program_loudness.h"
+#include "program_peaks.hpp"
 
 namespace omx {
 
@@ -64,6 +65,7 @@ struct PlResultArgs {
     uint64_t capacity;
     const PlStreamMeta* meta;
     const float* tp_max;
+    const omx_program_peak_record* peaks;  // null with peaks off; else max_true_peak_db = the larger of tp_max and the measured one
     omx_program_loudness_record* records;
     uint32_t n_streams;
     float floor_db;
@@ -83,12 +85,17 @@ public:
     int results(hipStream_t stream, const omx_program_loudness_record** d_records);
     int fetch(uint64_t stream_index, omx_program_loudness_record* dst);
     int fetch_segments(uint64_t stream_index, uint64_t first, uint64_t count, double* dst);
+    // include/omx/program_peaks.h (program_peaks.cpp)
+    int set_peaks(bool on);
+    int peaks(hipStream_t stream, const omx_program_peak_record** d_records);
+    int fetch_peaks(uint64_t stream_index, omx_program_peak_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
 private:
     void set_rate(float rate);
     void host_tables(hipStream_t stream);
+    void measure_peaks(const float* d_pcm, uint64_t frames_capacity, uint32_t max_frames, hipStream_t stream);
 
     omx_loudness_config cfg_{};
     uint32_t n_streams_;
@@ -110,6 +117,16 @@ private:
     bool dirty_ = true;
     int form_ = 0, last_form_ = 0;
     hipStream_t last_stream_ = nullptr;
+    // peaks: nothing is allocated or launched while they are off
+    bool peaks_on_ = false;
+    DeviceBuffer<omx_program_peak_record> peak_records_;
+    DeviceBuffer<float> peak_delay_;
+    DeviceBuffer<PkPartial> peak_partials_;
 };
 
 }  // namespace omx
+
+struct omx_program_loudness_bank {
+    omx::ProgramLoudnessBank impl;
+    omx_program_loudness_bank(const omx_loudness_config& c, uint32_t n, uint32_t cap) : impl(c, n, cap) {}
+};

@@ -465,7 +465,7 @@ __global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
         r.short_term_lufs = ms_to_lufs(r.short_term_energy, floor);
         r.max_momentary_lufs = ms_to_lufs(g_max, floor);
         r.max_short_term_lufs = ms_to_lufs(s_max, floor);
-        r.max_true_peak_db = a.tp_max[s];
+        r.max_true_peak_db = a.peaks ? fmaxf(a.tp_max[s], a.peaks[s].max_true_peak_db) : a.tp_max[s];
         r.overflow = meta.overflow;
         a.records[s] = r;
     }

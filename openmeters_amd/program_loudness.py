@@ -61,6 +61,45 @@ class ProgramLoudnessRecord:
     ENERGY_FIELDS = _ENERGIES
 
 
+_u64x8, _f32x8 = C.c_uint64 * 8, C.c_float * 8
+
+
+class CProgramPeakRecord(C.Structure):
+    """omx_program_peak_record (include/omx/program_peaks.h)"""
+    _fields_ = [("frames", C.c_uint64), ("true_peak_frame", _u64x8), ("sample_peak_frame", _u64x8), ("true_peak", _f32x8),
+                ("sample_peak", _f32x8), ("true_peak_db", _f32x8), ("sample_peak_db", _f32x8), ("max_true_peak_db", C.c_float),
+                ("max_sample_peak_db", C.c_float), ("max_true_peak_channel", C.c_uint32), ("oversampling", C.c_uint32),
+                ("channels", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(CProgramPeakRecord) == 288
+
+
+@dataclass
+class ProgramPeakRecord:
+    """omx_program_peak_record: per channel slot the maximum true peak and sample peak since the last reset (linear f32 and dB) with
+    the frame each first occurred at; arrays have 8 entries, slots at or above `channels` hold 0 / the floor."""
+    frames: int
+    true_peak_frame: np.ndarray      # uint64[8]
+    sample_peak_frame: np.ndarray
+    true_peak: np.ndarray            # float32[8]
+    sample_peak: np.ndarray
+    true_peak_db: np.ndarray
+    sample_peak_db: np.ndarray
+    max_true_peak_db: float
+    max_sample_peak_db: float
+    max_true_peak_channel: int
+    oversampling: int                # 4, 2 or 1; 0 until the stream takes a sample
+    channels: int
+
+    def tobytes(self) -> bytes:
+        """every field, bit for bit (records compare equal exactly when these do)"""
+        return b"".join([np.uint64(self.frames).tobytes(), self.true_peak_frame.tobytes(), self.sample_peak_frame.tobytes(),
+                         self.true_peak.tobytes(), self.sample_peak.tobytes(), self.true_peak_db.tobytes(), self.sample_peak_db.tobytes(),
+                         np.array([self.max_true_peak_db, self.max_sample_peak_db], np.float32).tobytes(),
+                         np.array([self.max_true_peak_channel, self.oversampling, self.channels], np.uint32).tobytes()])
+
+
 FORM_BY_SHAPE, FORM_REFERENCE_ORDER, FORM_TIME_PARALLEL = 0, 1, 2
 
 
@@ -134,6 +173,28 @@ class ProgramLoudnessBank:
         self.api.check(self.api.fn("program_loudness_bank_fetch", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, C.byref(r)))
         return ProgramLoudnessRecord(*[getattr(r, n) for n in _ENERGIES + _COUNTS + _LEVELS], bool(r.overflow))
+
+    def set_peaks(self, on: bool = True):
+        """Measure true peak and sample peak inside `process` (include/omx/program_peaks.h); off by default.  Only while no stream
+        holds samples: a new bank, or after reset() of every stream."""
+        self.api.check(self.api.fn("program_loudness_bank_set_peaks", C.c_int, [C.c_void_p, C.c_uint32])(self._h, 1 if on else 0))
+
+    def peaks(self, stream: int = 0) -> int:
+        """Device pointer to omx_program_peak_record[n_streams], valid until the next call on the bank."""
+        out = C.c_void_p()
+        self.api.check(self.api.fn("program_loudness_bank_peaks", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])(
+            self._h, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value
+
+    def fetch_peaks(self, stream_index: int) -> ProgramPeakRecord:
+        r = CProgramPeakRecord()
+        self.api.check(self.api.fn("program_loudness_bank_fetch_peaks", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, C.byref(r)))
+        return ProgramPeakRecord(int(r.frames), np.array(r.true_peak_frame[:], np.uint64), np.array(r.sample_peak_frame[:], np.uint64),
+                                 np.array(r.true_peak[:], np.float32), np.array(r.sample_peak[:], np.float32),
+                                 np.array(r.true_peak_db[:], np.float32), np.array(r.sample_peak_db[:], np.float32),
+                                 float(r.max_true_peak_db), float(r.max_sample_peak_db), int(r.max_true_peak_channel),
+                                 int(r.oversampling), int(r.channels))
 
     def fetch_segments(self, stream_index: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Stored segment energies e[first : first + count] of one stream (count None: up to the last stored one)."""
