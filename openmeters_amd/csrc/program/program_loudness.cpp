@@ -251,9 +251,7 @@ int ProgramLoudnessBank::note_snapshots(const omx_loudness_snapshot* d_snapshots
     return OMX_NONE;
 }
 
-int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_record** d_records) {
-    last_stream_ = stream;
-    meta_staging_.upload(h_meta_.data(), (size_t)n_streams_ * sizeof(PlStreamMeta), meta_.ptr, stream);
+PlResultArgs ProgramLoudnessBank::result_args() const {
     PlResultArgs r{};
     r.segments = segments_.ptr;
     r.capacity = capacity_;
@@ -264,7 +262,13 @@ int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_
     r.n_streams = n_streams_;
     r.floor_db = cfg_.floor_db;
     r.absolute_gate = std::pow(10.0, (-70.0 + 0.691) / 10.0);
-    launch_pl_results(r, stream);
+    return r;
+}
+
+int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_record** d_records) {
+    last_stream_ = stream;
+    meta_staging_.upload(h_meta_.data(), (size_t)n_streams_ * sizeof(PlStreamMeta), meta_.ptr, stream);
+    launch_pl_results(result_args(), stream);
     OMX_HIP(hipGetLastError());
     dirty_ = false;
     if (d_records) *d_records = records_.ptr;

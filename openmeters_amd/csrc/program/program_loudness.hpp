@@ -5,6 +5,7 @@
 #include "../common.hpp"
 #include "../../../include/omx/program_loudness.h"
 #include "program_peaks.hpp"
+#include "program_timeline.hpp"
 
 namespace omx {
 
@@ -89,12 +90,20 @@ public:
     int set_peaks(bool on);
     int peaks(hipStream_t stream, const omx_program_peak_record** d_records);
     int fetch_peaks(uint64_t stream_index, omx_program_peak_record* dst);
+    // include/omx/program_timeline.h (program_timeline.cpp)
+    int timeline(uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* d_rows, hipStream_t stream);
+    int fetch_timeline(uint64_t stream_index, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* dst);
+    int measure_intervals(const omx_program_interval* intervals, uint64_t n, hipStream_t stream, const omx_program_loudness_record** d_records);
+    int fetch_intervals(const omx_program_interval* intervals, uint64_t n, omx_program_loudness_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
 private:
     void set_rate(float rate);
     void host_tables(hipStream_t stream);
+    PlResultArgs result_args() const;
+    int timeline_rows(uint32_t stream_base, uint32_t n_streams, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* d_rows,
+                      hipStream_t stream);
     void measure_peaks(const float* d_pcm, uint64_t frames_capacity, uint32_t max_frames, hipStream_t stream);
 
     omx_loudness_config cfg_{};
@@ -122,6 +131,14 @@ private:
     DeviceBuffer<omx_program_peak_record> peak_records_;
     DeviceBuffer<float> peak_delay_;
     DeviceBuffer<PkPartial> peak_partials_;
+    // timeline and intervals: nothing is allocated or launched until one of their functions is called
+    DeviceBuffer<double> tl_gated_, tl_threshold_;
+    DeviceBuffer<uint32_t> tl_above_;
+    DeviceBuffer<omx_program_timeline_row> tl_rows_;  // fetch_timeline's device rows
+    DeviceBuffer<PlIntervalDesc> interval_descs_;
+    DeviceBuffer<omx_program_loudness_record> interval_records_;
+    std::vector<PlIntervalDesc> h_interval_descs_;
+    BlobStaging interval_staging_;
 };
 
 }  // namespace omx

@@ -300,8 +300,18 @@ __global__ __launch_bounds__(64) void pl_true_peak_fold_kernel(const omx_loudnes
     tp_max[s] = m;
 }
 
-// ---- result pass: one workgroup per stream over its stored segment energies
+// ---- result pass: one workgroup per stream (or per interval of a stream: include/omx/program_timeline.h) over stored segment energies
 constexpr uint32_t RT = 256;
+
+// What the pass works on: the whole of a stream (made from its PlStreamMeta) or a part of it (made from a PlIntervalDesc)
+struct PlResultDesc {
+    const double* e;       // the first segment energy
+    uint32_t n;            // how many
+    uint32_t overflow;
+    uint64_t frames;
+    const float* tp_max;   // max_true_peak_db = the larger of *tp_max and *tp_measured; null: the floor (a part has no peak of its own)
+    const float* tp_measured;  // null with peaks off
+};
 
 __device__ __forceinline__ double gating_block(const double* e, uint32_t j) {  // j >= 3
     return (((e[j - 3] + e[j - 2]) + e[j - 1]) + e[j]) * 0.25;
@@ -336,17 +346,16 @@ __device__ __forceinline__ double block_max(double v, double* red) {
     return r;
 }
 
-__global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
+__device__ __forceinline__ void pl_result_block(const PlResultDesc& d, double absolute_gate, float floor_db, omx_program_loudness_record* out) {
     __shared__ double red[RT];
     __shared__ uint32_t hist[2][256];
     __shared__ unsigned long long prefix[2];
     __shared__ uint32_t rank[2];
-    const uint32_t s = blockIdx.x, tid = threadIdx.x;
-    const PlStreamMeta meta = a.meta[s];
-    const uint32_t n = (uint32_t)min((uint64_t)meta.segments, a.capacity);
-    const double* e = a.segments + (uint64_t)s * a.capacity;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t n = d.n;
+    const double* e = d.e;
     const uint32_t ng = n >= 4 ? n - 3 : 0, ns = n >= 30 ? n - 29 : 0;
-    const double gate = a.absolute_gate;
+    const double gate = absolute_gate;
 
     // ---- gating blocks: maximum, mean above the absolute gate, mean above both gates
     double sum = 0.0, cnt = 0.0, mx = 0.0;
@@ -441,7 +450,7 @@ __global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
 
     if (tid == 0) {
         omx_program_loudness_record r{};
-        const float floor = a.floor_db;
+        const float floor = floor_db;
         r.integrated_energy = integrated;
         r.relative_threshold_energy = g_rel;
         r.lra_low_energy = lo_e;
@@ -450,7 +459,7 @@ __global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
         r.short_term_energy = ns ? short_term_block(e, n - 1) : 0.0;
         r.max_momentary_energy = g_max;
         r.max_short_term_energy = s_max;
-        r.frames = meta.frames;
+        r.frames = d.frames;
         r.segments = n;
         r.gating_blocks = ng;
         r.gating_above_absolute = (uint64_t)g_abs_cnt;
@@ -465,10 +474,36 @@ __global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
         r.short_term_lufs = ms_to_lufs(r.short_term_energy, floor);
         r.max_momentary_lufs = ms_to_lufs(g_max, floor);
         r.max_short_term_lufs = ms_to_lufs(s_max, floor);
-        r.max_true_peak_db = a.peaks ? fmaxf(a.tp_max[s], a.peaks[s].max_true_peak_db) : a.tp_max[s];
-        r.overflow = meta.overflow;
-        a.records[s] = r;
+        r.max_true_peak_db = !d.tp_max ? floor : (d.tp_measured ? fmaxf(*d.tp_max, *d.tp_measured) : *d.tp_max);
+        r.overflow = d.overflow;
+        *out = r;
     }
+}
+
+__global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
+    const uint32_t s = blockIdx.x;
+    const PlStreamMeta meta = a.meta[s];
+    PlResultDesc d;
+    d.e = a.segments + (uint64_t)s * a.capacity;
+    d.n = (uint32_t)min((uint64_t)meta.segments, a.capacity);
+    d.overflow = meta.overflow;
+    d.frames = meta.frames;
+    d.tp_max = a.tp_max + s;
+    d.tp_measured = a.peaks ? &a.peaks[s].max_true_peak_db : nullptr;
+    pl_result_block(d, a.absolute_gate, a.floor_db, a.records + s);
+}
+
+// One workgroup per interval: the same pass on e[first .. first + count) of a stream
+__global__ __launch_bounds__(RT) void pl_interval_kernel(PlResultArgs a, const PlIntervalDesc* descs) {
+    const PlIntervalDesc in = descs[blockIdx.x];
+    PlResultDesc d;
+    d.e = a.segments + in.offset;
+    d.n = in.n;
+    d.overflow = 0;
+    d.frames = in.frames;
+    d.tp_max = nullptr;
+    d.tp_measured = nullptr;
+    pl_result_block(d, a.absolute_gate, a.floor_db, a.records + blockIdx.x);
 }
 
 uint32_t segment_grid(const PlArgs& a) {
@@ -500,6 +535,9 @@ void launch_pl_commit(const PlArgs& a, hipStream_t stream) {
 }
 void launch_pl_results(const PlResultArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(pl_result_kernel, dim3(a.n_streams), dim3(RT), 0, stream, a);
+}
+void launch_pl_intervals(const PlResultArgs& a, const PlIntervalDesc* descs, uint32_t n, hipStream_t stream) {  // a.records: [n]
+    hipLaunchKernelGGL(pl_interval_kernel, dim3(n), dim3(RT), 0, stream, a, descs);
 }
 void launch_pl_true_peak_fold(const omx_loudness_snapshot* snapshots, uint64_t n_blocks, const uint32_t* d_n_blocks, uint32_t n_streams,
                               float* tp_max, hipStream_t stream) {

@@ -100,6 +100,30 @@ class ProgramPeakRecord:
                          np.array([self.max_true_peak_channel, self.oversampling, self.channels], np.uint32).tobytes()])
 
 
+class CProgramTimelineRow(C.Structure):
+    """omx_program_timeline_row (include/omx/program_timeline.h)"""
+    _fields_ = [("integrated_energy", C.c_double), ("relative_threshold_energy", C.c_double), ("momentary_lufs", C.c_float),
+                ("short_term_lufs", C.c_float), ("integrated_lufs", C.c_float), ("gating_above_absolute", C.c_uint32),
+                ("gating_above_relative", C.c_uint32), ("valid", C.c_uint32)]
+
+
+class CProgramInterval(C.Structure):
+    """omx_program_interval (include/omx/program_timeline.h)"""
+    _fields_ = [("stream", C.c_uint32), ("_pad", C.c_uint32), ("first_segment", C.c_uint64), ("segment_count", C.c_uint64)]
+
+
+assert C.sizeof(CProgramTimelineRow) == 40 and C.sizeof(CProgramInterval) == 24 and C.sizeof(CProgramLoudnessRecord) == 168
+
+# numpy views of the three structures (same layout: natural alignment, no padding but the named one)
+TIMELINE_ROW_DTYPE = np.dtype([("integrated_energy", "<f8"), ("relative_threshold_energy", "<f8"), ("momentary_lufs", "<f4"),
+                               ("short_term_lufs", "<f4"), ("integrated_lufs", "<f4"), ("gating_above_absolute", "<u4"),
+                               ("gating_above_relative", "<u4"), ("valid", "<u4")])
+INTERVAL_DTYPE = np.dtype([("stream", "<u4"), ("_pad", "<u4"), ("first_segment", "<u8"), ("segment_count", "<u8")])
+RECORD_DTYPE = np.dtype([(n, "<f8") for n in _ENERGIES] + [(n, "<u8") for n in _COUNTS] + [(n, "<f4") for n in _LEVELS]
+                        + [("overflow", "<u4"), ("_pad", "<u4")])
+assert TIMELINE_ROW_DTYPE.itemsize == 40 and INTERVAL_DTYPE.itemsize == 24 and RECORD_DTYPE.itemsize == 168
+
+
 FORM_BY_SHAPE, FORM_REFERENCE_ORDER, FORM_TIME_PARALLEL = 0, 1, 2
 
 
@@ -203,4 +227,48 @@ class ProgramLoudnessBank:
         out = np.zeros((max(count, 0),), np.float64)
         self.api.check(self.api.fn("program_loudness_bank_fetch_segments", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p])(
             self._h, stream_index, first, count, out.ctypes.data))
+        return out
+
+    # ---- include/omx/program_timeline.h
+    def timeline(self, d_rows: int, first: int = 0, stride: int = 1, count: int = 0, stream: int = 0) -> int:
+        """Rows j = first + i * stride, i < count, of every stream into the device buffer d_rows: omx_program_timeline_row
+        [n_streams][count] (TIMELINE_ROW_DTYPE, 40 bytes each), enqueued on `stream`.  Rows beyond a stream's end are the empty row."""
+        f = self.api.fn("program_loudness_bank_timeline", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p])
+        return self.api.check(f(self._h, first, stride, count, C.c_void_p(d_rows or 0), C.c_void_p(stream or 0)))
+
+    def fetch_timeline(self, stream_index: int, first: int = 0, stride: int = 1, count: Optional[int] = None) -> np.ndarray:
+        """The same rows of one stream as a numpy structured array (count None: up to the last stored segment); synchronises."""
+        if count is None:
+            segments = self.fetch(stream_index).segments
+            count = (segments - first + stride - 1) // stride if stride > 0 and segments > first else 0
+        out = np.zeros((max(count, 0),), TIMELINE_ROW_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_timeline", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, stream_index, first, stride, count, out.ctypes.data if count else None))
+        return out
+
+    @staticmethod
+    def _intervals(intervals) -> np.ndarray:
+        """(stream, first_segment, segment_count) triples, or an INTERVAL_DTYPE array, as omx_program_interval[n]"""
+        if isinstance(intervals, np.ndarray) and intervals.dtype == INTERVAL_DTYPE:
+            return np.ascontiguousarray(intervals)
+        out = np.zeros((len(intervals),), INTERVAL_DTYPE)
+        for i, (s, first, count) in enumerate(intervals):
+            out[i] = (s, 0, first, count)
+        return out
+
+    def measure_intervals(self, intervals, stream: int = 0) -> int:
+        """The programme record of every interval (stream, first_segment, segment_count), on `stream`; returns the device pointer to
+        omx_program_loudness_record[n] (0 for no interval), valid until the next call on the bank."""
+        arr = self._intervals(intervals)
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_measure_intervals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, arr.ctypes.data if len(arr) else None, len(arr), C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_intervals(self, intervals) -> np.ndarray:
+        """The same records as a numpy structured array (RECORD_DTYPE: the fields of omx_program_loudness_record); synchronises."""
+        arr = self._intervals(intervals)
+        out = np.zeros((len(arr),), RECORD_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_intervals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, arr.ctypes.data if len(arr) else None, len(arr), out.ctypes.data if len(arr) else None))
         return out
