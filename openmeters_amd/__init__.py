@@ -18,6 +18,7 @@ from .capi import (  # noqa: F401  (re-exported: the reference's config / snapsh
 from .program_loudness import ProgramLoudnessBank, ProgramLoudnessRecord  # noqa: F401  (include/omx/program_loudness.h)
 from .program_loudness import ProgramPeakRecord  # noqa: F401  (include/omx/program_peaks.h)
 from .program_loudness import CProgramTimelineRow, CProgramInterval  # noqa: F401  (include/omx/program_timeline.h)
+from .program_loudness import CProgramHistogram, ProgramHistogram, histogram_boundaries  # noqa: F401  (include/omx/program_histogram.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -51,8 +51,8 @@ void zero_input_step(DD (&g)[4], const double a[5]) {  // y = g0; g0' = g1 - a1 
 
 }  // namespace
 
-ProgramLoudnessBank::ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_t n_streams, uint32_t capacity_seconds)
-    : n_streams_(n_streams), capacity_((uint64_t)capacity_seconds * 10) {
+ProgramLoudnessBank::ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_t n_streams, uint32_t capacity_seconds, bool bounded)
+    : n_streams_(n_streams), capacity_(bounded ? 0 : (uint64_t)capacity_seconds * 10), bounded_(bounded) {
     cfg_ = cfg;
     const size_t slots = (size_t)n_streams * kPlSlots;
     state_.reserve(slots * 4);
@@ -66,6 +66,7 @@ ProgramLoudnessBank::ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_
     OMX_HIP(hipMemset(part_.ptr, 0, slots * sizeof(double)));
     h_meta_.assign(n_streams, PlStreamMeta{0, 0, 0});
     h_calls_.assign(n_streams, PlStreamCall{});
+    if (bounded_) bounded_init();
 }
 
 void ProgramLoudnessBank::set_rate(float rate) {
@@ -165,15 +166,15 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         PlStreamCall& c = h_calls_[s];
         c.reset = (reset_mask && reset_mask[s]) ? 1u : 0u;
         if (c.reset) m = PlStreamMeta{0, 0, 0};
-        const uint64_t room = capacity_ * seg_ - m.frames;  // a full stream takes no more samples
+        const uint64_t room = bounded_ ? ~0ull : capacity_ * seg_ - m.frames;  // a full stream takes no more samples; a bounded one never fills
         const uint64_t want = any ? (frames ? frames[s] : frames_capacity) : 0;
         c.frames = (uint32_t)std::min<uint64_t>(want, room);
         c.phase = seg_ ? (uint32_t)(m.frames % seg_) : 0u;
         c.n_new = seg_ ? (uint32_t)(((uint64_t)c.phase + c.frames) / seg_) : 0u;
-        c.seg_base = m.segments;
+        c.seg_base = bounded_ ? 0 : m.segments;  // bounded: the commit writes row s of the call's own scratch
         m.frames += c.frames;
         m.segments += c.n_new;
-        if (seg_ && m.segments >= capacity_) m.overflow = 1;
+        if (!bounded_ && seg_ && m.segments >= capacity_) m.overflow = 1;
         max_frames = std::max(max_frames, c.frames);
         max_new = std::max(max_new, c.n_new);
         taken = taken || c.frames != 0;
@@ -200,7 +201,13 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
     a.segments = segments_.ptr;
     a.capacity = capacity_;
     if (any_reset) launch_pl_reset(a, tp_max_.ptr, cfg_.floor_db, stream);
+    if (bounded_) {
+        fresh_.reserve((size_t)n_streams_ * std::max<uint32_t>(max_new, 1));
+        a.segments = fresh_.ptr;
+        a.capacity = max_new;
+    }
     if (!taken) {
+        if (bounded_ && any_reset) bounded_fold(0, stream);
         if (peaks_on_ && any_reset) measure_peaks(d_pcm, frames_capacity, 0, stream);  // (the flagged streams' peaks are cleared by the fold)
         OMX_HIP(hipGetLastError());
         return OMX_NONE;
@@ -236,6 +243,7 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         last_form_ = 1;
     }
     launch_pl_commit(a, stream);
+    if (bounded_ && (max_new != 0 || any_reset)) bounded_fold(max_new, stream);
     if (peaks_on_) measure_peaks(d_pcm, frames_capacity, max_frames, stream);
     OMX_HIP(hipGetLastError());
     return OMX_PRODUCED;
@@ -268,7 +276,8 @@ PlResultArgs ProgramLoudnessBank::result_args() const {
 int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_record** d_records) {
     last_stream_ = stream;
     meta_staging_.upload(h_meta_.data(), (size_t)n_streams_ * sizeof(PlStreamMeta), meta_.ptr, stream);
-    launch_pl_results(result_args(), stream);
+    if (bounded_) bounded_results(stream);
+    else launch_pl_results(result_args(), stream);
     OMX_HIP(hipGetLastError());
     dirty_ = false;
     if (d_records) *d_records = records_.ptr;
@@ -286,6 +295,7 @@ int ProgramLoudnessBank::fetch(uint64_t stream_index, omx_program_loudness_recor
 }
 
 int ProgramLoudnessBank::fetch_segments(uint64_t stream_index, uint64_t first, uint64_t count, double* dst) {
+    if (bounded_) return bounded_refusal("fetch_segments");
     if (stream_index >= n_streams_ || first > h_meta_[stream_index].segments || count > h_meta_[stream_index].segments - first) {
         set_last_error("program loudness fetch_segments: range outside the stored segments");
         return OMX_ERR_INVALID;

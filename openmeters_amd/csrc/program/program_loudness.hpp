@@ -6,6 +6,7 @@
 #include "../../../include/omx/program_loudness.h"
 #include "program_peaks.hpp"
 #include "program_timeline.hpp"
+#include "program_histogram.hpp"
 
 namespace omx {
 
@@ -78,7 +79,8 @@ void launch_pl_true_peak_fold(const omx_loudness_snapshot* snapshots, uint64_t n
 
 class ProgramLoudnessBank {
 public:
-    ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_t n_streams, uint32_t capacity_seconds);
+    // bounded: histogram storage (include/omx/program_histogram.h); capacity_seconds is not used then
+    ProgramLoudnessBank(const omx_loudness_config& cfg, uint32_t n_streams, uint32_t capacity_seconds, bool bounded = false);
     int reset(const uint8_t* reset_mask);
     int process(const float* d_pcm, uint64_t frames_capacity, const uint32_t* frames, const uint8_t* reset_mask, uint32_t channels,
                 float sample_rate, const uint8_t positions[OMX_MAX_CHANNELS], hipStream_t stream);
@@ -95,6 +97,9 @@ public:
     int fetch_timeline(uint64_t stream_index, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* dst);
     int measure_intervals(const omx_program_interval* intervals, uint64_t n, hipStream_t stream, const omx_program_loudness_record** d_records);
     int fetch_intervals(const omx_program_interval* intervals, uint64_t n, omx_program_loudness_record* dst);
+    // include/omx/program_histogram.h (program_histogram.cpp)
+    bool bounded() const { return bounded_; }
+    int fetch_histogram(uint64_t stream_index, omx_program_histogram* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -105,6 +110,10 @@ private:
     int timeline_rows(uint32_t stream_base, uint32_t n_streams, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* d_rows,
                       hipStream_t stream);
     void measure_peaks(const float* d_pcm, uint64_t frames_capacity, uint32_t max_frames, hipStream_t stream);
+    void bounded_init();
+    void bounded_fold(uint32_t max_new, hipStream_t stream);
+    void bounded_results(hipStream_t stream);
+    int bounded_refusal(const char* what) const;  // OMX_ERR_UNSUPPORTED for what needs the stored segments
 
     omx_loudness_config cfg_{};
     uint32_t n_streams_;
@@ -139,11 +148,16 @@ private:
     DeviceBuffer<omx_program_loudness_record> interval_records_;
     std::vector<PlIntervalDesc> h_interval_descs_;
     BlobStaging interval_staging_;
+    // bounded storage: nothing is allocated or launched unless the bank was created bounded
+    bool bounded_ = false;
+    DeviceBuffer<omx_program_histogram> hist_;
+    DeviceBuffer<PhRunning> running_;
+    DeviceBuffer<double> fresh_, boundaries_;  // fresh_: [n_streams][max_new] segments of the current call, grown on demand
 };
 
 }  // namespace omx
 
 struct omx_program_loudness_bank {
     omx::ProgramLoudnessBank impl;
-    omx_program_loudness_bank(const omx_loudness_config& c, uint32_t n, uint32_t cap) : impl(c, n, cap) {}
+    omx_program_loudness_bank(const omx_loudness_config& c, uint32_t n, uint32_t cap, bool bounded = false) : impl(c, n, cap, bounded) {}
 };

@@ -60,10 +60,12 @@ int ProgramLoudnessBank::timeline_rows(uint32_t stream_base, uint32_t n_streams,
 }
 
 int ProgramLoudnessBank::timeline(uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* d_rows, hipStream_t stream) {
+    if (bounded_) return bounded_refusal("timeline");
     return timeline_rows(0, n_streams_, first, stride, count, d_rows, stream);
 }
 
 int ProgramLoudnessBank::fetch_timeline(uint64_t stream_index, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* dst) {
+    if (bounded_) return bounded_refusal("fetch_timeline");
     if (stream_index >= n_streams_) {
         set_last_error("program loudness fetch_timeline: stream index out of range");
         return OMX_ERR_INVALID;
@@ -86,6 +88,7 @@ int ProgramLoudnessBank::fetch_timeline(uint64_t stream_index, uint64_t first, u
 
 int ProgramLoudnessBank::measure_intervals(const omx_program_interval* intervals, uint64_t n, hipStream_t stream,
                                            const omx_program_loudness_record** d_records) {
+    if (bounded_) return bounded_refusal("measure_intervals");
     if (n == 0) return OMX_NONE;
     if (!intervals || n > 0x7FFFFFFFull) {
         set_last_error("program loudness measure_intervals: null intervals (or more than 2^31 - 1)");
@@ -117,6 +120,7 @@ int ProgramLoudnessBank::measure_intervals(const omx_program_interval* intervals
 }
 
 int ProgramLoudnessBank::fetch_intervals(const omx_program_interval* intervals, uint64_t n, omx_program_loudness_record* dst) {
+    if (bounded_) return bounded_refusal("fetch_intervals");
     if (n == 0) return OMX_NONE;
     if (!dst) {
         set_last_error("program loudness fetch_intervals: null records");

@@ -124,17 +124,62 @@ RECORD_DTYPE = np.dtype([(n, "<f8") for n in _ENERGIES] + [(n, "<u8") for n in _
 assert TIMELINE_ROW_DTYPE.itemsize == 40 and INTERVAL_DTYPE.itemsize == 24 and RECORD_DTYPE.itemsize == 168
 
 
+HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
+_u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
+
+
+class CProgramHistogram(C.Structure):
+    """omx_program_histogram (include/omx/program_histogram.h)"""
+    _fields_ = [("gating_count", _u64xbins), ("gating_sum", _f64xbins), ("short_term_count", _u64xbins), ("short_term_sum", _f64xbins),
+                ("tail", C.c_double * HISTOGRAM_TAIL), ("segments", C.c_uint64), ("tail_count", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+assert C.sizeof(CProgramHistogram) == 32248
+
+
+@dataclass
+class ProgramHistogram:
+    """omx_program_histogram: what a stream of a bank with bounded storage keeps instead of its segments"""
+    gating_count: np.ndarray       # uint64[1000]
+    gating_sum: np.ndarray         # float64[1000]: sum of the block energies binned there
+    short_term_count: np.ndarray
+    short_term_sum: np.ndarray
+    tail: np.ndarray               # float64[tail_count]: the newest segment energies, oldest first
+    segments: int
+
+    def tobytes(self) -> bytes:
+        """every field, bit for bit"""
+        return b"".join([self.gating_count.tobytes(), self.gating_sum.tobytes(), self.short_term_count.tobytes(),
+                         self.short_term_sum.tobytes(), self.tail.tobytes(), np.uint64(self.segments).tobytes()])
+
+
+def histogram_boundaries(api: Api) -> np.ndarray:
+    """B[0 .. 1000] of include/omx/program_histogram.h: bin i is (B[i], B[i + 1]], B[0] the absolute gate.  Needs no device."""
+    out = np.zeros((HISTOGRAM_BINS + 1,), np.float64)
+    api.check(api.fn("program_histogram_boundaries", C.c_int, [C.c_void_p])(out.ctypes.data))
+    return out
+
+
 FORM_BY_SHAPE, FORM_REFERENCE_ORDER, FORM_TIME_PARALLEL = 0, 1, 2
 
 
 class ProgramLoudnessBank:
     """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
 
-    def __init__(self, api: Api, config: capi.LoudnessConfig, n_streams: int, channels: int = 2, capacity_seconds: int = 3600):
+    def __init__(self, api: Api, config: capi.LoudnessConfig, n_streams: int, channels: int = 2, capacity_seconds: int = 3600,
+                 storage: str = "segments"):
+        """storage "segments": one f64 per 100 ms segment, capacity_seconds per stream.  storage "histogram": bounded storage
+        (include/omx/program_histogram.h), about 32 KB per stream whatever the length, no overflow; capacity_seconds is not used."""
+        if storage not in ("segments", "histogram"):
+            raise ValueError(f"storage: {storage!r} is neither 'segments' nor 'histogram'")
         self.api = api
         self.n_streams = n_streams
         self._h = C.c_void_p()
         c = config.to_c()
+        if storage == "histogram":
+            api.check(api.fn("program_loudness_bank_create_bounded", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)])(
+                C.byref(c), n_streams, channels, C.byref(self._h)))
+            return
         api.check(api.fn("program_loudness_bank_create", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)])(
             C.byref(c), n_streams, channels, capacity_seconds, C.byref(self._h)))
 
@@ -228,6 +273,19 @@ class ProgramLoudnessBank:
         self.api.check(self.api.fn("program_loudness_bank_fetch_segments", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p])(
             self._h, stream_index, first, count, out.ctypes.data))
         return out
+
+    # ---- include/omx/program_histogram.h
+    def is_bounded(self) -> bool:
+        return bool(self.api.check(self.api.fn("program_loudness_bank_is_bounded", C.c_int, [C.c_void_p])(self._h)))
+
+    def fetch_histogram(self, stream_index: int) -> ProgramHistogram:
+        """One stream's histograms, tail and segment count (banks made with storage="histogram" only); synchronises."""
+        h = CProgramHistogram()
+        self.api.check(self.api.fn("program_loudness_bank_fetch_histogram", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, C.byref(h)))
+        return ProgramHistogram(np.array(h.gating_count[:], np.uint64), np.array(h.gating_sum[:], np.float64),
+                                np.array(h.short_term_count[:], np.uint64), np.array(h.short_term_sum[:], np.float64),
+                                np.array(h.tail[:h.tail_count], np.float64), int(h.segments))
 
     # ---- include/omx/program_timeline.h
     def timeline(self, d_rows: int, first: int = 0, stride: int = 1, count: int = 0, stream: int = 0) -> int:
