@@ -11,17 +11,13 @@
 // Result pass, one workgroup per stream: the 2 x 1000 bins go to LDS in parallel, lane 0 (gating) and lane 64 (short-term) add them in
 // ascending bin order as the definition says, the bin means and gate decisions are made in parallel in between.
 // Built with -ffp-contract=off like the rest of the bank.
-#include "program_loudness.hpp"
+#include "program_histogram_device.hpp"
 
 namespace omx {
 namespace {
 
 constexpr uint32_t PT = kPhThreads;
 constexpr uint32_t kNoBin = 0xFFFFu;
-
-__device__ __forceinline__ float ms_to_lufs(double ms, float floor) {  // as the stored mode's (program_loudness_kernels.hip)
-    return ms > 0.0 ? (float)fmax(fma(log10(ms), 10.0, -0.691), (double)floor) : floor;
-}
 
 // the largest i <= 999 with bnd[i] < z (z > bnd[0])
 __device__ __forceinline__ uint32_t find_bin(const double* bnd, double z) {
@@ -191,108 +187,29 @@ __global__ __launch_bounds__(PT) void ph_fold_kernel(PhFoldArgs a) {
     }
 }
 
-// ---- result pass
+// ---- result pass (the bins to the record: program_histogram_device.hpp, shared with the bounded group kernel)
 __global__ __launch_bounds__(PT) void ph_result_kernel(PhResultArgs a) {
-    __shared__ unsigned long long cnt[2][kPhBins];
-    __shared__ double sum[2][kPhBins];
-    __shared__ uint8_t pass[2][kPhBins];
-    __shared__ double threshold[2], pass_sum[2], lra_e[2];
-    __shared__ unsigned long long abs_cnt[2], pass_cnt[2];
+    __shared__ PhResultLds lds;
     const uint32_t s = blockIdx.x, tid = threadIdx.x;
     const omx_program_histogram& h = a.hist[s];
     for (uint32_t i = tid; i < kPhBins; i += PT) {
-        cnt[0][i] = h.gating_count[i];
-        sum[0][i] = h.gating_sum[i];
-        cnt[1][i] = h.short_term_count[i];
-        sum[1][i] = h.short_term_sum[i];
+        lds.cnt[0][i] = h.gating_count[i];
+        lds.sum[0][i] = h.gating_sum[i];
+        lds.cnt[1][i] = h.short_term_count[i];
+        lds.sum[1][i] = h.short_term_sum[i];
     }
     __syncthreads();
-    const bool adder = tid == 0 || tid == 64;  // one lane per histogram, in two wavefronts
-    const uint32_t which = tid >> 6;
-    if (adder) {
-        unsigned long long c = 0;
-        double z = 0.0;
-        for (uint32_t i = 0; i < kPhBins; ++i) {  // ascending i (an empty bin adds 0.0: the same bits)
-            c += cnt[which][i];
-            z += sum[which][i];
-        }
-        abs_cnt[which] = c;
-        threshold[which] = c ? (which ? 0.01 : 0.1) * (z / (double)c) : 0.0;
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < kPhBins; i += PT) {
-#pragma unroll
-        for (uint32_t w = 0; w < 2; ++w) pass[w][i] = cnt[w][i] != 0 && sum[w][i] / (double)cnt[w][i] > threshold[w];
-    }
-    __syncthreads();
-    if (adder) {
-        unsigned long long c = 0;
-        double z = 0.0;
-        for (uint32_t i = 0; i < kPhBins; ++i) {
-            if (!pass[which][i]) continue;
-            c += cnt[which][i];
-            z += sum[which][i];
-        }
-        pass_cnt[which] = c;
-        pass_sum[which] = z;
-        if (which == 1) {
-            double lo_e = 0.0, hi_e = 0.0;
-            if (c) {
-                const double n = (double)c;
-                const unsigned long long r_lo = (unsigned long long)floor((n - 1.0) * 0.10 + 0.5), r_hi = (unsigned long long)floor((n - 1.0) * 0.95 + 0.5);
-                unsigned long long below = 0;
-                bool have_lo = false, have_hi = false;
-                for (uint32_t i = 0; i < kPhBins && !have_hi; ++i) {
-                    if (!pass[1][i]) continue;
-                    const unsigned long long upto = below + cnt[1][i];
-                    if (!have_lo && r_lo < upto) {
-                        lo_e = sum[1][i] / (double)cnt[1][i];
-                        have_lo = true;
-                    }
-                    if (r_hi < upto) {
-                        hi_e = sum[1][i] / (double)cnt[1][i];
-                        have_hi = true;
-                    }
-                    below = upto;
-                }
-            }
-            lra_e[0] = lo_e;
-            lra_e[1] = hi_e;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
+    ph_result_from_bins(lds, a.floor_db, a.records + s, [&] {
         const PlStreamMeta meta = a.meta[s];
-        const PhRunning run = a.running[s];
-        const float floor = a.floor_db;
-        omx_program_loudness_record r{};
-        r.integrated_energy = pass_cnt[0] ? pass_sum[0] / (double)pass_cnt[0] : 0.0;
-        r.relative_threshold_energy = threshold[0];
-        r.lra_low_energy = lra_e[0];
-        r.lra_high_energy = lra_e[1];
-        r.momentary_energy = run.momentary;
-        r.short_term_energy = run.short_term;
-        r.max_momentary_energy = run.max_momentary;
-        r.max_short_term_energy = run.max_short_term;
-        r.frames = meta.frames;
-        r.segments = meta.segments;
-        r.gating_blocks = meta.segments >= 4 ? meta.segments - 3 : 0;
-        r.gating_above_absolute = abs_cnt[0];
-        r.gating_above_relative = pass_cnt[0];
-        r.short_term_blocks = meta.segments >= 30 ? meta.segments - 29 : 0;
-        r.short_term_above_absolute = abs_cnt[1];
-        r.short_term_above_relative = pass_cnt[1];
-        r.integrated_lufs = ms_to_lufs(r.integrated_energy, floor);
-        r.relative_threshold_lufs = ms_to_lufs(r.relative_threshold_energy, floor);
-        r.loudness_range_lu = pass_cnt[1] ? (float)(fma(log10(lra_e[1]), 10.0, -0.691) - fma(log10(lra_e[0]), 10.0, -0.691)) : 0.0f;
-        r.momentary_lufs = ms_to_lufs(r.momentary_energy, floor);
-        r.short_term_lufs = ms_to_lufs(r.short_term_energy, floor);
-        r.max_momentary_lufs = ms_to_lufs(r.max_momentary_energy, floor);
-        r.max_short_term_lufs = ms_to_lufs(r.max_short_term_energy, floor);
-        r.max_true_peak_db = a.peaks ? fmaxf(a.tp_max[s], a.peaks[s].max_true_peak_db) : a.tp_max[s];
-        r.overflow = 0;
-        a.records[s] = r;
-    }
+        PhRecordTail t;
+        t.run = a.running[s];
+        t.frames = meta.frames;
+        t.segments = meta.segments;
+        t.gating_blocks = meta.segments >= 4 ? meta.segments - 3 : 0;
+        t.short_term_blocks = meta.segments >= 30 ? meta.segments - 29 : 0;
+        t.max_true_peak_db = a.peaks ? fmaxf(a.tp_max[s], a.peaks[s].max_true_peak_db) : a.tp_max[s];
+        return t;
+    });
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 #include "program_peaks.hpp"
 #include "program_timeline.hpp"
 #include "program_histogram.hpp"
+#include "program_groups.hpp"
 
 namespace omx {
 
@@ -100,6 +101,11 @@ public:
     // include/omx/program_histogram.h (program_histogram.cpp)
     bool bounded() const { return bounded_; }
     int fetch_histogram(uint64_t stream_index, omx_program_histogram* dst);
+    // include/omx/program_groups.h (program_groups.cpp)
+    int measure_groups(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
+                       hipStream_t stream, const omx_program_loudness_record** d_records);
+    int fetch_groups(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
+                     omx_program_loudness_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -153,6 +159,12 @@ private:
     DeviceBuffer<omx_program_histogram> hist_;
     DeviceBuffer<PhRunning> running_;
     DeviceBuffer<double> fresh_, boundaries_;  // fresh_: [n_streams][max_new] segments of the current call, grown on demand
+    // groups: nothing is allocated or launched until measure_groups / fetch_groups is called; grow-only, kept until the bank goes
+    DeviceBuffer<uint8_t> group_tables_;  // [PgMember x n_members][PgGroup x n_groups] of the current call
+    DeviceBuffer<omx_program_loudness_record> group_records_;
+    DeviceBuffer<double> group_stage_;    // staged short-term blocks of the call's long groups (program_groups.hpp)
+    std::vector<uint8_t> h_group_tables_;
+    BlobStaging group_staging_;
 };
 
 }  // namespace omx

@@ -12,7 +12,7 @@
 //                     weights, (B) scan of the 4 x 4 zero-input transition over the items, (C) the items again from their true start
 //                     states, summing into the (at most two) segments they overlap, (D) fold of those sums in item order.
 // Built with -ffp-contract=off: the recurrence rounds like the reference's scalar code; fused multiply-adds are spelled out.
-#include "program_loudness.hpp"
+#include "program_result_device.hpp"
 
 namespace omx {
 namespace {
@@ -21,9 +21,6 @@ constexpr uint32_t TF = kPlTile;
 constexpr int kTileLoads = 32;                    // dwords per lane and tile: 64 lanes x 32 = 64 slots x 32 frames
 constexpr uint32_t kTileFloats = 64 * TF + 64;    // the largest tile: (64 >> shift) rows of TF * channels + (1 << shift) floats
 
-__device__ __forceinline__ float ms_to_lufs(double ms, float floor) {  // loudness/processor.rs:57-66
-    return ms > 0.0 ? (float)fmax(fma(log10(ms), 10.0, -0.691), (double)floor) : floor;
-}
 __device__ __forceinline__ void flush_denormals(double (&f)[4]) {  // level.rs:14-18
 #pragma unroll
     for (int k = 0; k < 4; ++k)
@@ -300,210 +297,24 @@ __global__ __launch_bounds__(64) void pl_true_peak_fold_kernel(const omx_loudnes
     tp_max[s] = m;
 }
 
-// ---- result pass: one workgroup per stream (or per interval of a stream: include/omx/program_timeline.h) over stored segment energies
-constexpr uint32_t RT = 256;
-
-// What the pass works on: the whole of a stream (made from its PlStreamMeta) or a part of it (made from a PlIntervalDesc)
-struct PlResultDesc {
-    const double* e;       // the first segment energy
-    uint32_t n;            // how many
-    uint32_t overflow;
-    uint64_t frames;
-    const float* tp_max;   // max_true_peak_db = the larger of *tp_max and *tp_measured; null: the floor (a part has no peak of its own)
-    const float* tp_measured;  // null with peaks off
-};
-
-__device__ __forceinline__ double gating_block(const double* e, uint32_t j) {  // j >= 3
-    return (((e[j - 3] + e[j - 2]) + e[j - 1]) + e[j]) * 0.25;
-}
-__device__ __forceinline__ double short_term_block(const double* e, uint32_t j) {  // j >= 29
-    double acc = e[j - 29];
-#pragma unroll
-    for (uint32_t k = 1; k < 30; ++k) acc += e[j - 29 + k];
-    return acc / 30.0;
-}
-// workgroup reductions in a fixed order (lane-strided partials, then a binary tree)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t d = RT / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] += red[threadIdx.x + d];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double block_max(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t d = RT / 2; d > 0; d >>= 1) {
-        if (threadIdx.x < d) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + d]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ void pl_result_block(const PlResultDesc& d, double absolute_gate, float floor_db, omx_program_loudness_record* out) {
-    __shared__ double red[RT];
-    __shared__ uint32_t hist[2][256];
-    __shared__ unsigned long long prefix[2];
-    __shared__ uint32_t rank[2];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t n = d.n;
-    const double* e = d.e;
-    const uint32_t ng = n >= 4 ? n - 3 : 0, ns = n >= 30 ? n - 29 : 0;
-    const double gate = absolute_gate;
-
-    // ---- gating blocks: maximum, mean above the absolute gate, mean above both gates
-    double sum = 0.0, cnt = 0.0, mx = 0.0;
-    for (uint32_t j = 3 + tid; j < n; j += RT) {
-        const double g = gating_block(e, j);
-        mx = fmax(mx, g);
-        if (g > gate) {
-            sum += g;
-            cnt += 1.0;
-        }
-    }
-    const double g_max = block_max(mx, red);
-    const double g_abs_sum = block_sum(sum, red), g_abs_cnt = block_sum(cnt, red);  // (counts < 2^53: exact)
-    const double g_rel = g_abs_cnt > 0.0 ? 0.1 * (g_abs_sum / g_abs_cnt) : 0.0;
-    sum = 0.0;
-    cnt = 0.0;
-    for (uint32_t j = 3 + tid; j < n; j += RT) {
-        const double g = gating_block(e, j);
-        if (g > gate && g > g_rel) {
-            sum += g;
-            cnt += 1.0;
-        }
-    }
-    const double g_rel_sum = block_sum(sum, red), g_rel_cnt = block_sum(cnt, red);
-    const double integrated = g_rel_cnt > 0.0 ? g_rel_sum / g_rel_cnt : 0.0;
-
-    // ---- short-term blocks: maximum, relative gate, survivors
-    sum = 0.0;
-    cnt = 0.0;
-    mx = 0.0;
-    for (uint32_t j = 29 + tid; j < n; j += RT) {
-        const double v = short_term_block(e, j);
-        mx = fmax(mx, v);
-        if (v > gate) {
-            sum += v;
-            cnt += 1.0;
-        }
-    }
-    const double s_max = block_max(mx, red);
-    const double s_abs_sum = block_sum(sum, red), s_abs_cnt = block_sum(cnt, red);
-    const double s_rel = s_abs_cnt > 0.0 ? 0.01 * (s_abs_sum / s_abs_cnt) : 0.0;
-    cnt = 0.0;
-    for (uint32_t j = 29 + tid; j < n; j += RT) {
-        const double v = short_term_block(e, j);
-        if (v > gate && v > s_rel) cnt += 1.0;
-    }
-    const double s_rel_cnt = block_sum(cnt, red);
-
-    // ---- loudness range: the two nearest-rank elements of the survivors by radix select on the f64 bit patterns (energies are
-    // non-negative, so the patterns order like the values), eight bits per pass, both ranks in the same passes
-    double lo_e = 0.0, hi_e = 0.0;
-    if (s_rel_cnt > 0.0) {
-        if (tid == 0) {
-            prefix[0] = prefix[1] = 0ull;
-            rank[0] = (uint32_t)floor((s_rel_cnt - 1.0) * 0.10 + 0.5);
-            rank[1] = (uint32_t)floor((s_rel_cnt - 1.0) * 0.95 + 0.5);
-        }
-        for (int pass = 0; pass < 8; ++pass) {
-            const int shift = 56 - 8 * pass;
-            const unsigned long long done = pass == 0 ? 0ull : ~0ull << (shift + 8);
-            hist[0][tid] = 0;
-            hist[1][tid] = 0;
-            __syncthreads();
-            const unsigned long long pre0 = prefix[0], pre1 = prefix[1];
-            for (uint32_t j = 29 + tid; j < n; j += RT) {
-                const double v = short_term_block(e, j);
-                if (v > gate && v > s_rel) {
-                    const unsigned long long key = (unsigned long long)__double_as_longlong(v);
-                    const uint32_t digit = (uint32_t)(key >> shift) & 255u;
-                    if ((key & done) == pre0) atomicAdd(&hist[0][digit], 1u);
-                    if ((key & done) == pre1) atomicAdd(&hist[1][digit], 1u);
-                }
-            }
-            __syncthreads();
-            if (tid < 2) {
-                uint32_t r = rank[tid], below = 0;
-                for (uint32_t d = 0; d < 256; ++d) {
-                    const uint32_t h = hist[tid][d];
-                    if (r < below + h) {
-                        prefix[tid] |= (unsigned long long)d << shift;
-                        rank[tid] = r - below;
-                        break;
-                    }
-                    below += h;
-                }
-            }
-            __syncthreads();
-        }
-        lo_e = __longlong_as_double((long long)prefix[0]);
-        hi_e = __longlong_as_double((long long)prefix[1]);
-    }
-
-    if (tid == 0) {
-        omx_program_loudness_record r{};
-        const float floor = floor_db;
-        r.integrated_energy = integrated;
-        r.relative_threshold_energy = g_rel;
-        r.lra_low_energy = lo_e;
-        r.lra_high_energy = hi_e;
-        r.momentary_energy = ng ? gating_block(e, n - 1) : 0.0;
-        r.short_term_energy = ns ? short_term_block(e, n - 1) : 0.0;
-        r.max_momentary_energy = g_max;
-        r.max_short_term_energy = s_max;
-        r.frames = d.frames;
-        r.segments = n;
-        r.gating_blocks = ng;
-        r.gating_above_absolute = (uint64_t)g_abs_cnt;
-        r.gating_above_relative = (uint64_t)g_rel_cnt;
-        r.short_term_blocks = ns;
-        r.short_term_above_absolute = (uint64_t)s_abs_cnt;
-        r.short_term_above_relative = (uint64_t)s_rel_cnt;
-        r.integrated_lufs = ms_to_lufs(integrated, floor);
-        r.relative_threshold_lufs = ms_to_lufs(g_rel, floor);
-        r.loudness_range_lu = s_rel_cnt > 0.0 ? (float)(fma(log10(hi_e), 10.0, -0.691) - fma(log10(lo_e), 10.0, -0.691)) : 0.0f;
-        r.momentary_lufs = ms_to_lufs(r.momentary_energy, floor);
-        r.short_term_lufs = ms_to_lufs(r.short_term_energy, floor);
-        r.max_momentary_lufs = ms_to_lufs(g_max, floor);
-        r.max_short_term_lufs = ms_to_lufs(s_max, floor);
-        r.max_true_peak_db = !d.tp_max ? floor : (d.tp_measured ? fmaxf(*d.tp_max, *d.tp_measured) : *d.tp_max);
-        r.overflow = d.overflow;
-        *out = r;
-    }
-}
+// ---- result pass: one workgroup per stream (or per interval of a stream: include/omx/program_timeline.h) over stored segment energies.
+// The pass itself (block expressions, reductions, radix select, record writer) is program_result_device.hpp, shared with the group kernel.
+constexpr uint32_t RT = kPlResultThreads;
 
 __global__ __launch_bounds__(RT) void pl_result_kernel(PlResultArgs a) {
     const uint32_t s = blockIdx.x;
     const PlStreamMeta meta = a.meta[s];
-    PlResultDesc d;
-    d.e = a.segments + (uint64_t)s * a.capacity;
-    d.n = (uint32_t)min((uint64_t)meta.segments, a.capacity);
-    d.overflow = meta.overflow;
-    d.frames = meta.frames;
-    d.tp_max = a.tp_max + s;
-    d.tp_measured = a.peaks ? &a.peaks[s].max_true_peak_db : nullptr;
-    pl_result_block(d, a.absolute_gate, a.floor_db, a.records + s);
+    const PlSpanSource src{a.segments + (uint64_t)s * a.capacity, (uint32_t)min((uint64_t)meta.segments, a.capacity)};
+    const PlRecordTail tail{meta.frames, meta.overflow, a.tp_max + s, a.peaks ? &a.peaks[s].max_true_peak_db : nullptr};
+    pl_result_pass(src, tail, a.absolute_gate, a.floor_db, a.records + s);
 }
 
 // One workgroup per interval: the same pass on e[first .. first + count) of a stream
 __global__ __launch_bounds__(RT) void pl_interval_kernel(PlResultArgs a, const PlIntervalDesc* descs) {
     const PlIntervalDesc in = descs[blockIdx.x];
-    PlResultDesc d;
-    d.e = a.segments + in.offset;
-    d.n = in.n;
-    d.overflow = 0;
-    d.frames = in.frames;
-    d.tp_max = nullptr;
-    d.tp_measured = nullptr;
-    pl_result_block(d, a.absolute_gate, a.floor_db, a.records + blockIdx.x);
+    const PlSpanSource src{a.segments + in.offset, in.n};
+    const PlRecordTail tail{in.frames, 0u, nullptr, nullptr};
+    pl_result_pass(src, tail, a.absolute_gate, a.floor_db, a.records + blockIdx.x);
 }
 
 uint32_t segment_grid(const PlArgs& a) {

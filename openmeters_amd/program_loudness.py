@@ -124,6 +124,16 @@ RECORD_DTYPE = np.dtype([(n, "<f8") for n in _ENERGIES] + [(n, "<u8") for n in _
 assert TIMELINE_ROW_DTYPE.itemsize == 40 and INTERVAL_DTYPE.itemsize == 24 and RECORD_DTYPE.itemsize == 168
 
 
+class CProgramGroup(C.Structure):
+    """omx_program_group (include/omx/program_groups.h): members[first_member : first_member + member_count]"""
+    _fields_ = [("first_member", C.c_uint64), ("member_count", C.c_uint64)]
+
+
+GROUP_DTYPE = np.dtype([("first_member", "<u8"), ("member_count", "<u8")])
+TO_END = 2 ** 64 - 1   # OMX_PROGRAM_TO_END, as a member's segment_count: up to the stream's last stored segment
+assert C.sizeof(CProgramGroup) == 16 and GROUP_DTYPE.itemsize == 16
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -329,4 +339,37 @@ class ProgramLoudnessBank:
         out = np.zeros((len(arr),), RECORD_DTYPE)
         f = self.api.fn("program_loudness_bank_fetch_intervals", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p])
         self.api.check(f(self._h, arr.ctypes.data if len(arr) else None, len(arr), out.ctypes.data if len(arr) else None))
+        return out
+
+    # ---- include/omx/program_groups.h
+    @staticmethod
+    def _groups(groups) -> np.ndarray:
+        """(first_member, member_count) pairs, or a GROUP_DTYPE array, as omx_program_group[n]"""
+        if isinstance(groups, np.ndarray) and groups.dtype == GROUP_DTYPE:
+            return np.ascontiguousarray(groups)
+        out = np.zeros((len(groups),), GROUP_DTYPE)
+        for i, (first, count) in enumerate(groups):
+            out[i] = (first, count)
+        return out
+
+    def measure_groups(self, members, groups, stream: int = 0) -> int:
+        """The record of every group measured as ONE programme (album loudness and range), on `stream`.  members: (stream,
+        first_segment, segment_count) triples or an INTERVAL_DTYPE array, segment_count may be TO_END; groups: (first_member,
+        member_count) pairs or a GROUP_DTYPE array, ranges of the member table that may overlap.  Returns the device pointer to
+        omx_program_loudness_record[n_groups] (0 for no group), valid until the next call on the bank."""
+        m, g = self._intervals(members), self._groups(groups)
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_measure_groups", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_groups(self, members, groups) -> np.ndarray:
+        """The same records as a numpy structured array (RECORD_DTYPE), one per group; synchronises."""
+        m, g = self._intervals(members), self._groups(groups)
+        out = np.zeros((len(g),), RECORD_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_groups", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         out.ctypes.data if len(g) else None))
         return out
