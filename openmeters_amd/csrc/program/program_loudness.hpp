@@ -8,6 +8,7 @@
 #include "program_timeline.hpp"
 #include "program_histogram.hpp"
 #include "program_groups.hpp"
+#include "program_normalize.hpp"
 
 namespace omx {
 
@@ -106,6 +107,15 @@ public:
                        hipStream_t stream, const omx_program_loudness_record** d_records);
     int fetch_groups(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
                      omx_program_loudness_record* dst);
+    // include/omx/program_normalize.h (program_normalize.cpp)
+    int plan_gains(const omx_program_gain_rule* rule, hipStream_t stream, const omx_program_gain_record** d_gains);
+    int plan_group_gains(const omx_program_gain_rule* rule, const omx_program_interval* members, uint64_t n_members,
+                         const omx_program_group* groups, uint64_t n_groups, hipStream_t stream, const omx_program_gain_record** d_gains);
+    int fetch_gains(uint64_t first, uint64_t count, omx_program_gain_record* dst);
+    int apply_gains(const float* d_in, float* d_out, uint64_t frames_capacity, const uint32_t* frames, uint32_t channels,
+                    const omx_program_gain_record* d_gains, uint64_t n_gains, const uint32_t* gain_of_stream, hipStream_t stream,
+                    const omx_program_apply_record** d_applied);
+    int fetch_applied(uint64_t stream_index, omx_program_apply_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -165,6 +175,14 @@ private:
     DeviceBuffer<double> group_stage_;    // staged short-term blocks of the call's long groups (program_groups.hpp)
     std::vector<uint8_t> h_group_tables_;
     BlobStaging group_staging_;
+    // normalisation: nothing is allocated or launched until a plan_* / apply_gains call; grow-only, kept until the bank goes
+    DeviceBuffer<omx_program_gain_record> gain_records_;  // the last plan's records
+    uint64_t gains_planned_ = 0;                          // how many of them (0: no plan yet)
+    DeviceBuffer<PnStreamCall> apply_calls_;
+    DeviceBuffer<omx_program_apply_record> apply_records_;
+    std::vector<PnStreamCall> h_apply_calls_;
+    BlobStaging apply_staging_;
+    bool applied_ = false;
 };
 
 }  // namespace omx

@@ -134,6 +134,59 @@ TO_END = 2 ** 64 - 1   # OMX_PROGRAM_TO_END, as a member's segment_count: up to 
 assert C.sizeof(CProgramGroup) == 16 and GROUP_DTYPE.itemsize == 16
 
 
+class CProgramGainRule(C.Structure):
+    """omx_program_gain_rule (include/omx/program_normalize.h)"""
+    _fields_ = [("target_lufs", C.c_float), ("true_peak_ceiling_db", C.c_float), ("min_gain_db", C.c_float), ("max_gain_db", C.c_float),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramGainRecord(C.Structure):
+    """omx_program_gain_record (include/omx/program_normalize.h)"""
+    _fields_ = [("gain_db", C.c_float), ("gain", C.c_float), ("source_lufs", C.c_float), ("source_peak_db", C.c_float),
+                ("predicted_lufs", C.c_float), ("predicted_peak_db", C.c_float), ("limited_by", C.c_uint32), ("peak_known", C.c_uint32)]
+
+
+class CProgramApplyRecord(C.Structure):
+    """omx_program_apply_record (include/omx/program_normalize.h)"""
+    _fields_ = [("frames", C.c_uint64), ("samples_over", C.c_uint64), ("gain", C.c_float), ("out_sample_peak", C.c_float),
+                ("out_sample_peak_db", C.c_float), ("gain_index", C.c_uint32)]
+
+
+GAIN_RECORD_DTYPE = np.dtype([("gain_db", "<f4"), ("gain", "<f4"), ("source_lufs", "<f4"), ("source_peak_db", "<f4"),
+                              ("predicted_lufs", "<f4"), ("predicted_peak_db", "<f4"), ("limited_by", "<u4"), ("peak_known", "<u4")])
+APPLY_RECORD_DTYPE = np.dtype([("frames", "<u8"), ("samples_over", "<u8"), ("gain", "<f4"), ("out_sample_peak", "<f4"),
+                               ("out_sample_peak_db", "<f4"), ("gain_index", "<u4")])
+assert C.sizeof(CProgramGainRule) == 24 and C.sizeof(CProgramGainRecord) == 32 and C.sizeof(CProgramApplyRecord) == 32
+assert GAIN_RECORD_DTYPE.itemsize == 32 and APPLY_RECORD_DTYPE.itemsize == 32
+UNITY_GAIN = 2 ** 32 - 1   # OMX_PROGRAM_UNITY_GAIN, as a gain index of apply_gains: factor 1
+GAIN_LIMIT_PEAK = 1        # GainRule.flags
+GAIN_BY_TARGET, GAIN_BY_PEAK, GAIN_BY_MAX_GAIN, GAIN_BY_MIN_GAIN, GAIN_BY_NO_MEASUREMENT = 0, 1, 2, 3, 4
+
+
+@dataclass
+class GainRule:
+    """omx_program_gain_rule: the target, the clamp and, with flags = GAIN_LIMIT_PEAK, the true-peak ceiling"""
+    target_lufs: float = -23.0
+    true_peak_ceiling_db: float = -1.0
+    min_gain_db: float = -60.0
+    max_gain_db: float = 60.0
+    flags: int = 0
+
+    def to_c(self) -> CProgramGainRule:
+        return CProgramGainRule(self.target_lufs, self.true_peak_ceiling_db, self.min_gain_db, self.max_gain_db, self.flags, 0)
+
+
+def evaluate_gain(api: Api, rule: GainRule, integrated_lufs: float, gating_above_relative: int, max_true_peak_db: float,
+                  floor_db: float) -> np.ndarray:
+    """The gain record the plan kernels write for these source values (omx_program_gain_evaluate), as a GAIN_RECORD_DTYPE scalar.
+    Needs no device."""
+    out = np.zeros((1,), GAIN_RECORD_DTYPE)
+    c = rule.to_c()
+    api.check(api.fn("program_gain_evaluate", C.c_int, [C.c_void_p, C.c_float, C.c_uint64, C.c_float, C.c_float, C.c_void_p])(
+        C.byref(c), integrated_lufs, gating_above_relative, max_true_peak_db, floor_db, out.ctypes.data))
+    return out[0]
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -373,3 +426,61 @@ class ProgramLoudnessBank:
         self.api.check(f(self._h, m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
                          out.ctypes.data if len(g) else None))
         return out
+
+    # ---- include/omx/program_normalize.h
+    def plan_gains(self, rule: GainRule, stream: int = 0) -> int:
+        """One gain per stream (track gain) from the bank's own records, on `stream`; returns the device pointer to
+        omx_program_gain_record[n_streams] (GAIN_RECORD_DTYPE), valid until the next plan call on the bank."""
+        out, c = C.c_void_p(), rule.to_c()
+        self.api.check(self.api.fn("program_loudness_bank_plan_gains", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])(
+            self._h, C.byref(c), C.c_void_p(stream or 0), C.byref(out)))
+        self._planned = self.n_streams
+        return out.value or 0
+
+    def plan_group_gains(self, rule: GainRule, members, groups, stream: int = 0) -> int:
+        """One gain per group (album gain): measure_groups of `members` / `groups`, then the gain of every group record with the
+        largest true peak of the group's member streams.  Returns the device pointer to omx_program_gain_record[n_groups] (0 for no
+        group), valid until the next plan call on the bank."""
+        m, g = self._intervals(members), self._groups(groups)
+        out, c = C.c_void_p(), rule.to_c()
+        f = self.api.fn("program_loudness_bank_plan_group_gains", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.byref(c), m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         C.c_void_p(stream or 0), C.byref(out)))
+        if len(g):
+            self._planned = len(g)
+        return out.value or 0
+
+    def fetch_gains(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Records [first, first + count) of the last plan as a GAIN_RECORD_DTYPE array (count None: up to the plan's last record);
+        synchronises."""
+        if count is None:
+            count = max(getattr(self, "_planned", 0) - first, 0)
+        out = np.zeros((count,), GAIN_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_gains", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p])(
+            self._h, first, count, out.ctypes.data if count else None))
+        return out
+
+    def apply_gains(self, d_in: int, d_out: int, frames_capacity: int, channels: int, d_gains: int, n_gains: int,
+                    frames: Optional[Sequence[int]] = None, gain_of_stream: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """d_out[s][f][c] = d_in[s][f][c] * gain of stream s, for f < frames[s], on `stream` (d_out == d_in: in place).  d_gains:
+        device pointer to n_gains omx_program_gain_record (a plan call's, or the caller's own); gain_of_stream[s]: the record of
+        stream s, UNITY_GAIN for factor 1, None: stream s uses record s.  Returns the device pointer to
+        omx_program_apply_record[n_streams] (APPLY_RECORD_DTYPE), written fresh by every call."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        gi = self._per_stream(gain_of_stream, np.uint32, "gain_of_stream")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_apply_gains", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                         C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), C.c_void_p(d_out or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                         channels, C.c_void_p(d_gains or 0), n_gains, gi.ctypes.data if gi is not None else None, C.c_void_p(stream or 0),
+                         C.byref(out)))
+        return out.value or 0
+
+    def fetch_applied(self, stream_index: int) -> np.ndarray:
+        """One stream's record of the last apply_gains call as an APPLY_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), APPLY_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_applied", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
