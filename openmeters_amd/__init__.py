@@ -22,6 +22,8 @@ from .program_loudness import CProgramHistogram, ProgramHistogram, histogram_bou
 from .program_loudness import CProgramGroup, GROUP_DTYPE, TO_END  # noqa: F401  (include/omx/program_groups.h)
 from .program_loudness import (  # noqa: F401  (include/omx/program_normalize.h)
     APPLY_RECORD_DTYPE, GAIN_RECORD_DTYPE, UNITY_GAIN, CProgramApplyRecord, CProgramGainRecord, CProgramGainRule, GainRule, evaluate_gain)
+from .program_loudness import (  # noqa: F401  (include/omx/program_limit.h)
+    LIMIT_RECORD_DTYPE, CProgramLimitRecord, CProgramLimitRule, LimitRule, limit_latency)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -9,6 +9,7 @@
 #include "program_histogram.hpp"
 #include "program_groups.hpp"
 #include "program_normalize.hpp"
+#include "program_limit.hpp"
 
 namespace omx {
 
@@ -116,6 +117,13 @@ public:
                     const omx_program_gain_record* d_gains, uint64_t n_gains, const uint32_t* gain_of_stream, hipStream_t stream,
                     const omx_program_apply_record** d_applied);
     int fetch_applied(uint64_t stream_index, omx_program_apply_record* dst);
+    // include/omx/program_limit.h (program_limit.cpp)
+    int limiter_configure(const omx_program_limit_rule* rule, uint32_t channels, float sample_rate);
+    int limiter_reset(const uint8_t* reset_mask);
+    int apply_limited(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
+                      const uint8_t* flush_mask, const omx_program_gain_record* d_gains, uint64_t n_gains, const uint32_t* gain_of_stream,
+                      hipStream_t stream, const omx_program_limit_record** d_limited);
+    int fetch_limited(uint64_t stream_index, omx_program_limit_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -183,6 +191,9 @@ private:
     std::vector<PnStreamCall> h_apply_calls_;
     BlobStaging apply_staging_;
     bool applied_ = false;
+    // limiter: nothing is allocated or launched until limiter_configure
+    LmArgs limiter_args() const;
+    std::unique_ptr<ProgramLimiter> limiter_;
 };
 
 }  // namespace omx

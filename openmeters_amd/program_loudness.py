@@ -187,6 +187,46 @@ def evaluate_gain(api: Api, rule: GainRule, integrated_lufs: float, gating_above
     return out[0]
 
 
+class CProgramLimitRule(C.Structure):
+    """omx_program_limit_rule (include/omx/program_limit.h)"""
+    _fields_ = [("ceiling_db", C.c_float), ("attack_frames", C.c_uint32), ("release_hold_frames", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CProgramLimitRecord(C.Structure):
+    """omx_program_limit_record (include/omx/program_limit.h)"""
+    _fields_ = [("frames_in", C.c_uint64), ("frames_out", C.c_uint64), ("frames_written", C.c_uint64), ("frames_limited", C.c_uint64),
+                ("samples_over", C.c_uint64), ("gain", C.c_float), ("ceiling", C.c_float), ("min_envelope", C.c_float),
+                ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float), ("max_reduction_db", C.c_float),
+                ("gain_index", C.c_uint32), ("state", C.c_uint32), ("latency_frames", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+LIMIT_RECORD_DTYPE = np.dtype([("frames_in", "<u8"), ("frames_out", "<u8"), ("frames_written", "<u8"), ("frames_limited", "<u8"),
+                               ("samples_over", "<u8"), ("gain", "<f4"), ("ceiling", "<f4"), ("min_envelope", "<f4"),
+                               ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"), ("max_reduction_db", "<f4"),
+                               ("gain_index", "<u4"), ("state", "<u4"), ("latency_frames", "<u4"), ("_pad", "<u4")])
+assert C.sizeof(CProgramLimitRule) == 16 and C.sizeof(CProgramLimitRecord) == 80 and LIMIT_RECORD_DTYPE.itemsize == 80
+LIMIT_IDLE, LIMIT_RUNNING, LIMIT_FLUSHED = 0, 1, 2   # omx_program_limit_record.state
+
+
+@dataclass
+class LimitRule:
+    """omx_program_limit_rule: the true-peak ceiling, the attack (look-ahead) and the hold before the release, in frames"""
+    ceiling_db: float = -1.0
+    attack_frames: int = 64
+    release_hold_frames: int = 0
+    flags: int = 0
+
+    def to_c(self) -> CProgramLimitRule:
+        return CProgramLimitRule(self.ceiling_db, self.attack_frames, self.release_hold_frames, self.flags)
+
+
+def limit_latency(api: Api, rule: LimitRule) -> int:
+    """Frames by which the limiter's output trails its input (omx_program_limit_latency): attack_frames + 23.  Needs no device."""
+    out, c = C.c_uint32(), rule.to_c()
+    api.check(api.fn("program_limit_latency", C.c_int, [C.c_void_p, C.c_void_p])(C.byref(c), C.byref(out)))
+    return int(out.value)
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -482,5 +522,46 @@ class ProgramLoudnessBank:
         """One stream's record of the last apply_gains call as an APPLY_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), APPLY_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_applied", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_limit.h
+    def configure_limiter(self, rule: LimitRule, channels: int, sample_rate: float):
+        """Set the limiter's rule and the format of the PCM it takes; allocates its state.  Only while no stream of the limiter holds
+        frames: a new bank, or after reset_limiter() of every stream."""
+        c = rule.to_c()
+        self.api.check(self.api.fn("program_loudness_bank_limiter_configure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float])(
+            self._h, C.byref(c), channels, sample_rate))
+
+    def reset_limiter(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the limiter start over (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_limiter_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def apply_limited(self, d_in: int, frames_capacity: int, d_out: int, out_capacity: int, d_gains: int, n_gains: int,
+                      frames: Optional[Sequence[int]] = None, flush_mask: Optional[Sequence[int]] = None,
+                      gain_of_stream: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels]) into the look-ahead limiter and write what it
+        emits to d_out[s][0 ..) (f32 [n_streams][out_capacity][channels]): the frames taken limit_latency() frames earlier, scaled by
+        the stream's gain and the limiter's envelope; with the stream flagged in flush_mask, everything it still holds.  Gains and
+        gain_of_stream as apply_gains; the gain is read when a stream takes its first frame after a reset.  Returns the device pointer
+        to omx_program_limit_record[n_streams] (LIMIT_RECORD_DTYPE); `frames_written` says how many frames each stream got."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        fl = self._per_stream(flush_mask, np.uint8, "flush_mask")
+        gi = self._per_stream(gain_of_stream, np.uint32, "gain_of_stream")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_apply_limited", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(d_out or 0),
+                         out_capacity, fl.ctypes.data if fl is not None else None, C.c_void_p(d_gains or 0), n_gains,
+                         gi.ctypes.data if gi is not None else None, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_limited(self, stream_index: int) -> np.ndarray:
+        """One stream's limiter record as a LIMIT_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), LIMIT_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_limited", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
