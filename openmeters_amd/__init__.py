@@ -24,6 +24,9 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_normalize.h)
     APPLY_RECORD_DTYPE, GAIN_RECORD_DTYPE, UNITY_GAIN, CProgramApplyRecord, CProgramGainRecord, CProgramGainRule, GainRule, evaluate_gain)
 from .program_loudness import (  # noqa: F401  (include/omx/program_limit.h)
     LIMIT_RECORD_DTYPE, CProgramLimitRecord, CProgramLimitRule, LimitRule, limit_latency)
+from .program_loudness import (  # noqa: F401  (include/omx/program_pcm.h)
+    DITHER_NONE, DITHER_TPDF, EXPORT_RECORD_DTYPE, PCM_S16, PCM_S24, PCM_S32, CProgramExportRecord, CProgramExportRule, ExportRule,
+    dither_value, pcm_format_bytes)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

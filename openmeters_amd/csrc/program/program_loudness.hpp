@@ -10,6 +10,7 @@
 #include "program_groups.hpp"
 #include "program_normalize.hpp"
 #include "program_limit.hpp"
+#include "program_pcm.hpp"
 
 namespace omx {
 
@@ -124,6 +125,14 @@ public:
                       const uint8_t* flush_mask, const omx_program_gain_record* d_gains, uint64_t n_gains, const uint32_t* gain_of_stream,
                       hipStream_t stream, const omx_program_limit_record** d_limited);
     int fetch_limited(uint64_t stream_index, omx_program_limit_record* dst);
+    // include/omx/program_pcm.h (program_pcm.cpp)
+    int import_pcm(const void* d_in, uint32_t format, float* d_out, uint64_t frames_capacity, const uint32_t* frames, uint32_t channels,
+                   hipStream_t stream);
+    int export_configure(const omx_program_export_rule* rule, uint32_t channels);
+    int export_reset(const uint8_t* reset_mask);
+    int export_pcm(const float* d_in, void* d_out, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
+                   const omx_program_export_record** d_exported);
+    int fetch_exported(uint64_t stream_index, omx_program_export_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -194,6 +203,11 @@ private:
     // limiter: nothing is allocated or launched until limiter_configure
     LmArgs limiter_args() const;
     std::unique_ptr<ProgramLimiter> limiter_;
+    // PCM formats: nothing is allocated or launched until import_pcm / export_configure
+    DeviceBuffer<PcStreamCall> import_calls_;
+    std::vector<PcStreamCall> h_import_calls_;
+    BlobStaging import_staging_;
+    std::unique_ptr<ProgramExporter> exporter_;
 };
 
 }  // namespace omx

@@ -227,6 +227,52 @@ def limit_latency(api: Api, rule: LimitRule) -> int:
     return int(out.value)
 
 
+class CProgramExportRule(C.Structure):
+    """omx_program_export_rule (include/omx/program_pcm.h)"""
+    _fields_ = [("format", C.c_uint32), ("dither", C.c_uint32), ("seed", C.c_uint64), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramExportRecord(C.Structure):
+    """omx_program_export_record (include/omx/program_pcm.h)"""
+    _fields_ = [("frames_out", C.c_uint64), ("frames_written", C.c_uint64), ("samples_clipped", C.c_uint64), ("samples_nan", C.c_uint64),
+                ("out_peak", C.c_uint32), ("out_peak_db", C.c_float), ("format", C.c_uint32), ("dither", C.c_uint32)]
+
+
+EXPORT_RECORD_DTYPE = np.dtype([("frames_out", "<u8"), ("frames_written", "<u8"), ("samples_clipped", "<u8"), ("samples_nan", "<u8"),
+                                ("out_peak", "<u4"), ("out_peak_db", "<f4"), ("format", "<u4"), ("dither", "<u4")])
+assert C.sizeof(CProgramExportRule) == 24 and C.sizeof(CProgramExportRecord) == 48 and EXPORT_RECORD_DTYPE.itemsize == 48
+PCM_S16, PCM_S24, PCM_S32 = 1, 2, 3     # OMX_PCM_*: 2, 3 (packed) and 4 bytes per sample, little-endian, interleaved
+DITHER_NONE, DITHER_TPDF = 0, 1         # OMX_DITHER_*
+
+
+@dataclass
+class ExportRule:
+    """omx_program_export_rule: the integer format, the dither and its seed"""
+    format: int = PCM_S16
+    dither: int = DITHER_TPDF
+    seed: int = 0
+    flags: int = 0
+
+    def to_c(self) -> CProgramExportRule:
+        return CProgramExportRule(self.format, self.dither, self.seed, self.flags, 0)
+
+
+def pcm_format_bytes(api: Api, format: int) -> int:
+    """Bytes per sample of a PCM_* format (omx_pcm_format_bytes).  Needs no device."""
+    out = C.c_uint32()
+    api.check(api.fn("pcm_format_bytes", C.c_int, [C.c_uint32, C.c_void_p])(format, C.byref(out)))
+    return int(out.value)
+
+
+def dither_value(api: Api, rule: ExportRule, stream: int, frame: int, channel: int) -> float:
+    """The dither, in LSB, that the export adds to (stream, absolute frame, channel) under `rule` (omx_program_dither_evaluate): the
+    function the kernel runs.  Needs no device."""
+    out, c = C.c_double(), rule.to_c()
+    api.check(api.fn("program_dither_evaluate", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p])(
+        C.byref(c), stream, frame, channel, C.byref(out)))
+    return float(out.value)
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -563,5 +609,49 @@ class ProgramLoudnessBank:
         """One stream's limiter record as a LIMIT_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), LIMIT_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_limited", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_pcm.h
+    def import_pcm(self, d_in: int, format: int, d_out: int, frames_capacity: int, channels: int,
+                   frames: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """d_out[s][f][c] (f32) = the integer sample d_in[s][f][c] of `format` (PCM_S16 / PCM_S24 / PCM_S32, little-endian, rows of
+        frames_capacity * channels samples without padding, base 4-byte aligned) scaled to [-1, 1), for f < frames[s], on `stream`.
+        Out of place.  Returns 1 when any stream brought a frame, else 0."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        f = self.api.fn("program_loudness_bank_import_pcm", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p])
+        return self.api.check(f(self._h, C.c_void_p(d_in or 0), format, C.c_void_p(d_out or 0), frames_capacity,
+                                fr.ctypes.data if fr is not None else None, channels, C.c_void_p(stream or 0)))
+
+    def configure_export(self, rule: ExportRule, channels: int):
+        """Set the export's format, dither and seed and the channel count of the PCM it takes; allocates its records.  Only while every
+        stream's export position is 0: a new bank, or after reset_export() of every stream."""
+        c = rule.to_c()
+        self.api.check(self.api.fn("program_loudness_bank_export_configure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])(
+            self._h, C.byref(c), channels))
+
+    def reset_export(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the export start over at dither position 0 with a zero record (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_export_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def export_pcm(self, d_in: int, d_out: int, frames_capacity: int, frames: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """d_out[s][f][c] (integer PCM of the configured format, base 4-byte aligned) = d_in[s][f][c] (f32) scaled, dithered at the
+        stream's running position, rounded and clamped, for f < frames[s], on `stream`.  Out of place; no byte beyond a stream's
+        frames is written.  Returns the device pointer to omx_program_export_record[n_streams] (EXPORT_RECORD_DTYPE)."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_export_pcm", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), C.c_void_p(d_out or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                         C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_exported(self, stream_index: int) -> np.ndarray:
+        """One stream's export record as an EXPORT_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), EXPORT_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_exported", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
