@@ -27,6 +27,9 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_limit.h)
 from .program_loudness import (  # noqa: F401  (include/omx/program_pcm.h)
     DITHER_NONE, DITHER_TPDF, EXPORT_RECORD_DTYPE, PCM_S16, PCM_S24, PCM_S32, CProgramExportRecord, CProgramExportRule, ExportRule,
     dither_value, pcm_format_bytes)
+from .program_loudness import (  # noqa: F401  (include/omx/program_resample.h)
+    RESAMPLE_INFO_DTYPE, RESAMPLE_RECORD_DTYPE, CProgramResampleInfo, CProgramResampleRecord, CProgramResampleRule, ResampleRule,
+    resample_frames, resample_plan, resample_taps)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -11,6 +11,7 @@
 #include "program_normalize.hpp"
 #include "program_limit.hpp"
 #include "program_pcm.hpp"
+#include "program_resample.hpp"
 
 namespace omx {
 
@@ -133,6 +134,12 @@ public:
     int export_pcm(const float* d_in, void* d_out, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
                    const omx_program_export_record** d_exported);
     int fetch_exported(uint64_t stream_index, omx_program_export_record* dst);
+    // include/omx/program_resample.h (program_resample.cpp)
+    int resampler_configure(const omx_program_resample_rule* rule, uint32_t channels);
+    int resampler_reset(const uint8_t* reset_mask);
+    int resample(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
+                 const uint8_t* flush_mask, hipStream_t stream, const omx_program_resample_record** d_resampled);
+    int fetch_resampled(uint64_t stream_index, omx_program_resample_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -208,6 +215,9 @@ private:
     std::vector<PcStreamCall> h_import_calls_;
     BlobStaging import_staging_;
     std::unique_ptr<ProgramExporter> exporter_;
+    // sample-rate conversion: nothing is allocated or launched until resampler_configure
+    RsArgs resampler_args() const;
+    std::unique_ptr<ProgramResampler> resampler_;
 };
 
 }  // namespace omx

@@ -273,6 +273,75 @@ def dither_value(api: Api, rule: ExportRule, stream: int, frame: int, channel: i
     return float(out.value)
 
 
+class CProgramResampleRule(C.Structure):
+    """omx_program_resample_rule (include/omx/program_resample.h)"""
+    _fields_ = [("rate_in", C.c_uint32), ("rate_out", C.c_uint32), ("half_width", C.c_uint32), ("beta", C.c_float), ("cutoff", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class CProgramResampleInfo(C.Structure):
+    """omx_program_resample_info (include/omx/program_resample.h)"""
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("taps", C.c_uint32), ("latency_frames", C.c_uint32), ("table_floats", C.c_uint64),
+                ("tile_frames", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramResampleRecord(C.Structure):
+    """omx_program_resample_record (include/omx/program_resample.h)"""
+    _fields_ = [("frames_in", C.c_uint64), ("frames_out", C.c_uint64), ("frames_written", C.c_uint64), ("samples_over", C.c_uint64),
+                ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float), ("state", C.c_uint32), ("L", C.c_uint32),
+                ("M", C.c_uint32), ("taps", C.c_uint32), ("latency_frames", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+RESAMPLE_INFO_DTYPE = np.dtype([("L", "<u4"), ("M", "<u4"), ("taps", "<u4"), ("latency_frames", "<u4"), ("table_floats", "<u8"),
+                                ("tile_frames", "<u4"), ("_pad", "<u4")])
+RESAMPLE_RECORD_DTYPE = np.dtype([("frames_in", "<u8"), ("frames_out", "<u8"), ("frames_written", "<u8"), ("samples_over", "<u8"),
+                                  ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"), ("state", "<u4"), ("L", "<u4"), ("M", "<u4"),
+                                  ("taps", "<u4"), ("latency_frames", "<u4"), ("_pad", "<u4")])
+assert C.sizeof(CProgramResampleRule) == 24 and C.sizeof(CProgramResampleInfo) == 32 and C.sizeof(CProgramResampleRecord) == 64
+assert RESAMPLE_INFO_DTYPE.itemsize == 32 and RESAMPLE_RECORD_DTYPE.itemsize == 64
+RESAMPLE_IDLE, RESAMPLE_RUNNING, RESAMPLE_FLUSHED = 0, 1, 2   # omx_program_resample_record.state
+
+
+@dataclass
+class ResampleRule:
+    """omx_program_resample_rule: the two rates in whole Hz, the filter's half width in zero crossings, Kaiser beta and the -6 dB
+    point as a fraction of the narrower Nyquist; the defaults are the header's"""
+    rate_in: int = 44100
+    rate_out: int = 48000
+    half_width: int = 32
+    beta: float = 12.0
+    cutoff: float = 0.94
+    flags: int = 0
+
+    def to_c(self) -> CProgramResampleRule:
+        return CProgramResampleRule(self.rate_in, self.rate_out, self.half_width, self.beta, self.cutoff, self.flags)
+
+
+def resample_plan(api: Api, rule: ResampleRule) -> np.ndarray:
+    """The plan of `rule` (omx_program_resample_plan) as a RESAMPLE_INFO_DTYPE scalar: L, M, taps per phase, the latency H in input
+    frames, the table's size in floats and the main kernel's tile in output frames.  Needs no device."""
+    out, c = np.zeros((1,), RESAMPLE_INFO_DTYPE), rule.to_c()
+    api.check(api.fn("program_resample_plan", C.c_int, [C.c_void_p, C.c_void_p])(C.byref(c), out.ctypes.data))
+    return out[0]
+
+
+def resample_taps(api: Api, rule: ResampleRule) -> np.ndarray:
+    """The f32 table [L][taps] the kernel uses under `rule` (omx_program_resample_taps).  Needs no device."""
+    info, c = resample_plan(api, rule), rule.to_c()
+    out = np.zeros((int(info["L"]), int(info["taps"])), np.float32)
+    api.check(api.fn("program_resample_taps", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64])(C.byref(c), out.ctypes.data, out.size))
+    return out
+
+
+def resample_frames(api: Api, rule: ResampleRule, frames_in_before: int, frames_out_before: int, frames: int, flush: bool = False) -> int:
+    """Frames a stream emits in a call that brings `frames` frames, after frames_in_before taken and frames_out_before emitted
+    (omx_program_resample_frames): what d_out has to hold.  Needs no device."""
+    out, c = C.c_uint64(), rule.to_c()
+    api.check(api.fn("program_resample_frames", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p])(
+        C.byref(c), frames_in_before, frames_out_before, frames, 1 if flush else 0, C.byref(out)))
+    return int(out.value)
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -653,5 +722,42 @@ class ProgramLoudnessBank:
         """One stream's export record as an EXPORT_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), EXPORT_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_exported", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_resample.h
+    def configure_resampler(self, rule: ResampleRule, channels: int):
+        """Set the resampler's rule and the channel count of the PCM it takes; builds its table and allocates its state.  Only while
+        no stream of the resampler holds frames: a new bank, or after reset_resampler() of every stream."""
+        c = rule.to_c()
+        self.api.check(self.api.fn("program_loudness_bank_resampler_configure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])(
+            self._h, C.byref(c), channels))
+
+    def reset_resampler(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the resampler start over (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_resampler_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def resample(self, d_in: int, frames_capacity: int, d_out: int, out_capacity: int, frames: Optional[Sequence[int]] = None,
+                 flush_mask: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels], at rate_in) and write the frames at rate_out
+        that they complete to d_out[s][0 ..) (f32 [n_streams][out_capacity][channels]); with the stream flagged in flush_mask, the
+        tail as well (the input continued with zeros).  resample_frames() says how many frames a call emits.  Out of place.  Returns
+        the device pointer to omx_program_resample_record[n_streams] (RESAMPLE_RECORD_DTYPE); `frames_written` says how many frames
+        each stream got."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        fl = self._per_stream(flush_mask, np.uint8, "flush_mask")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_resample", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(d_out or 0),
+                         out_capacity, fl.ctypes.data if fl is not None else None, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_resampled(self, stream_index: int) -> np.ndarray:
+        """One stream's resampler record as a RESAMPLE_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), RESAMPLE_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_resampled", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
