@@ -30,6 +30,9 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_pcm.h)
 from .program_loudness import (  # noqa: F401  (include/omx/program_resample.h)
     RESAMPLE_INFO_DTYPE, RESAMPLE_RECORD_DTYPE, CProgramResampleInfo, CProgramResampleRecord, CProgramResampleRule, ResampleRule,
     resample_frames, resample_plan, resample_taps)
+from .program_loudness import (  # noqa: F401  (include/omx/program_remix.h)
+    REMIX_INFO_DTYPE, REMIX_KIND_MONO, REMIX_KIND_STEREO, REMIX_MAX_MATRICES, REMIX_NORMALIZE, REMIX_RECORD_DTYPE, CProgramDownmixRule,
+    CProgramRemixInfo, CProgramRemixRecord, DownmixRule, remix_downmix, remix_plan, remix_select)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

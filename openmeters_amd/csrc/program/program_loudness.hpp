@@ -12,6 +12,7 @@
 #include "program_limit.hpp"
 #include "program_pcm.hpp"
 #include "program_resample.hpp"
+#include "program_remix.hpp"
 
 namespace omx {
 
@@ -140,6 +141,11 @@ public:
     int resample(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
                  const uint8_t* flush_mask, hipStream_t stream, const omx_program_resample_record** d_resampled);
     int fetch_resampled(uint64_t stream_index, omx_program_resample_record* dst);
+    // include/omx/program_remix.h (program_remix.cpp)
+    int remix_configure(uint32_t channels_in, uint32_t channels_out, const float* matrices, uint32_t n_matrices);
+    int remix(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, const uint32_t* matrix_of_stream,
+              hipStream_t stream, const omx_program_remix_record** d_remixed);
+    int fetch_remixed(uint64_t stream_index, omx_program_remix_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -218,6 +224,9 @@ private:
     // sample-rate conversion: nothing is allocated or launched until resampler_configure
     RsArgs resampler_args() const;
     std::unique_ptr<ProgramResampler> resampler_;
+    // channel remix: nothing is allocated or launched until remix_configure
+    RmArgs remix_args() const;
+    std::unique_ptr<ProgramRemix> remix_;
 };
 
 }  // namespace omx

@@ -342,6 +342,76 @@ def resample_frames(api: Api, rule: ResampleRule, frames_in_before: int, frames_
     return int(out.value)
 
 
+class CProgramRemixInfo(C.Structure):
+    """omx_program_remix_info (include/omx/program_remix.h)"""
+    _fields_ = [("tile_frames", C.c_uint32), ("channels_in", C.c_uint32), ("channels_out", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramDownmixRule(C.Structure):
+    """omx_program_downmix_rule (include/omx/program_remix.h)"""
+    _fields_ = [("kind", C.c_uint32), ("center_level", C.c_float), ("surround_level", C.c_float), ("lfe_level", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+class CProgramRemixRecord(C.Structure):
+    """omx_program_remix_record (include/omx/program_remix.h)"""
+    _fields_ = [("frames", C.c_uint64), ("samples_over", C.c_uint64), ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float),
+                ("matrix_index", C.c_uint32), ("terms", C.c_uint32)]
+
+
+REMIX_INFO_DTYPE = np.dtype([("tile_frames", "<u4"), ("channels_in", "<u4"), ("channels_out", "<u4"), ("_pad", "<u4")])
+REMIX_RECORD_DTYPE = np.dtype([("frames", "<u8"), ("samples_over", "<u8"), ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"),
+                               ("matrix_index", "<u4"), ("terms", "<u4")])
+assert C.sizeof(CProgramRemixInfo) == 16 and C.sizeof(CProgramDownmixRule) == 20 and C.sizeof(CProgramRemixRecord) == 32
+assert REMIX_INFO_DTYPE.itemsize == 16 and REMIX_RECORD_DTYPE.itemsize == 32
+REMIX_MAX_MATRICES = 65536
+REMIX_KIND_STEREO, REMIX_KIND_MONO = 0, 1   # omx_program_downmix_rule.kind
+REMIX_NORMALIZE = 1                          # omx_program_downmix_rule.flags
+
+
+@dataclass
+class DownmixRule:
+    """omx_program_downmix_rule: the kind of fold-down (REMIX_KIND_STEREO: Lo/Ro, REMIX_KIND_MONO: its mono fold), the levels of the
+    centre, the surrounds and the LFE, and REMIX_NORMALIZE or 0; the defaults are the header's"""
+    kind: int = REMIX_KIND_STEREO
+    center_level: float = 0.70710678
+    surround_level: float = 0.70710678
+    lfe_level: float = 0.0
+    flags: int = 0
+
+    def to_c(self) -> CProgramDownmixRule:
+        return CProgramDownmixRule(self.kind, self.center_level, self.surround_level, self.lfe_level, self.flags)
+
+
+def remix_plan(api: Api, channels_in: int, channels_out: int) -> np.ndarray:
+    """The plan of a channel pair (omx_program_remix_plan) as a REMIX_INFO_DTYPE scalar: the main kernel's tile in frames.  Needs no
+    device."""
+    out = np.zeros((1,), REMIX_INFO_DTYPE)
+    api.check(api.fn("program_remix_plan", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p])(channels_in, channels_out, out.ctypes.data))
+    return out[0]
+
+
+def remix_downmix(api: Api, rule: DownmixRule, channels_in: int, positions_in: Sequence[int]):
+    """The fold-down of a layout given as positions (omx_program_remix_downmix) -> (matrix f32 [channels_out][channels_in], positions_out
+    as a list of 8).  Needs no device."""
+    c, pos = rule.to_c(), _u8x8(*(list(positions_in) + [capi.POS_UNKNOWN] * 8)[:8])
+    matrix, n_out, pos_out = np.zeros((2 * 8,), np.float32), C.c_uint32(), _u8x8()
+    api.check(api.fn("program_remix_downmix", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])(
+        C.byref(c), channels_in, pos, matrix.ctypes.data, C.byref(n_out), pos_out))
+    return matrix[:n_out.value * channels_in].reshape(n_out.value, channels_in).copy(), list(pos_out)
+
+
+def remix_select(api: Api, channels_in: int, positions_in: Sequence[int], channels_out: int, positions_out: Sequence[int]):
+    """The matrix that gives every output position the first input channel of that position (omx_program_remix_select) ->
+    (matrix f32 [channels_out][channels_in], the mask of the outputs without a source).  Needs no device."""
+    pos_in = _u8x8(*(list(positions_in) + [capi.POS_UNKNOWN] * 8)[:8])
+    pos_out = _u8x8(*(list(positions_out) + [capi.POS_UNKNOWN] * 8)[:8])
+    matrix, missing = np.zeros((8 * 8,), np.float32), C.c_uint32()
+    api.check(api.fn("program_remix_select", C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])(
+        channels_in, pos_in, channels_out, pos_out, matrix.ctypes.data, C.byref(missing)))
+    return matrix[:channels_out * channels_in].reshape(channels_out, channels_in).copy(), int(missing.value)
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -759,5 +829,39 @@ class ProgramLoudnessBank:
         """One stream's resampler record as a RESAMPLE_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), RESAMPLE_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_resampled", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_remix.h
+    def configure_remix(self, matrices, channels_in: int, channels_out: int):
+        """Upload the mixing matrices, one f32 [channels_out][channels_in] array or a stack [n][channels_out][channels_in], and
+        allocate the records.  Allowed at any time; remix calls still enqueued are waited for before an earlier table goes."""
+        m = np.ascontiguousarray(matrices, dtype=np.float32)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[1:] != (channels_out, channels_in):
+            raise ValueError(f"matrices: shape {m.shape} is neither [{channels_out}][{channels_in}] nor a stack of it")
+        self.api.check(self.api.fn("program_loudness_bank_remix_configure", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32])(
+            self._h, channels_in, channels_out, m.ctypes.data if m.size else None, m.shape[0]))
+
+    def remix(self, d_in: int, d_out: int, frames_capacity: int, frames: Optional[Sequence[int]] = None,
+              matrix_of_stream: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """d_out[s][f][o] (f32 [n_streams][frames_capacity][channels_out]) = the mix of d_in[s][f][:] (f32
+        [n_streams][frames_capacity][channels_in]) under the matrix of stream s, for f < frames[s], on `stream`.  matrix_of_stream[s]:
+        the matrix of stream s, None: matrix 0 for every stream.  Out of place; no float beyond a stream's frames is written.  Returns
+        the device pointer to omx_program_remix_record[n_streams] (REMIX_RECORD_DTYPE), written fresh by every call."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        mi = self._per_stream(matrix_of_stream, np.uint32, "matrix_of_stream")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_remix", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(d_out or 0),
+                         mi.ctypes.data if mi is not None else None, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_remixed(self, stream_index: int) -> np.ndarray:
+        """One stream's record of the last remix call as a REMIX_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), REMIX_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_remixed", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
