@@ -33,6 +33,11 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_resample.h)
 from .program_loudness import (  # noqa: F401  (include/omx/program_remix.h)
     REMIX_INFO_DTYPE, REMIX_KIND_MONO, REMIX_KIND_STEREO, REMIX_MAX_MATRICES, REMIX_NORMALIZE, REMIX_RECORD_DTYPE, CProgramDownmixRule,
     CProgramRemixInfo, CProgramRemixRecord, DownmixRule, remix_downmix, remix_plan, remix_select)
+from .program_loudness import (  # noqa: F401  (include/omx/program_inspect.h)
+    INSPECT_ALL_SILENT, INSPECT_ANTIPHASE, INSPECT_CLIPPED, INSPECT_DB_FLOOR, INSPECT_DC, INSPECT_DROPOUT, INSPECT_INFO_DTYPE,
+    INSPECT_MAX_PAIRS, INSPECT_NAN, INSPECT_RECORD_DTYPE, INSPECT_SUMMARY_DTYPE, CProgramInspectChannel, CProgramInspectInfo,
+    CProgramInspectPair, CProgramInspectRecord, CProgramInspectRule, CProgramInspectSummary, InspectRule, inspect_plan,
+    inspect_rule_default, inspect_summarize)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -13,6 +13,7 @@
 #include "program_pcm.hpp"
 #include "program_resample.hpp"
 #include "program_remix.hpp"
+#include "program_inspect.hpp"
 
 namespace omx {
 
@@ -146,6 +147,12 @@ public:
     int remix(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, const uint32_t* matrix_of_stream,
               hipStream_t stream, const omx_program_remix_record** d_remixed);
     int fetch_remixed(uint64_t stream_index, omx_program_remix_record* dst);
+    // include/omx/program_inspect.h (program_inspect.cpp)
+    int inspect_configure(const omx_program_inspect_rule* rule, uint32_t channels, const uint32_t* pairs, uint32_t n_pairs);
+    int inspect_reset(const uint8_t* reset_mask);
+    int inspect(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
+                const omx_program_inspect_record** d_inspected);
+    int fetch_inspected(uint64_t stream_index, omx_program_inspect_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -227,6 +234,9 @@ private:
     // channel remix: nothing is allocated or launched until remix_configure
     RmArgs remix_args() const;
     std::unique_ptr<ProgramRemix> remix_;
+    // signal QC: nothing is allocated or launched until inspect_configure
+    InArgs inspect_args() const;
+    std::unique_ptr<ProgramInspector> inspector_;
 };
 
 }  // namespace omx

@@ -412,6 +412,107 @@ def remix_select(api: Api, channels_in: int, positions_in: Sequence[int], channe
     return matrix[:channels_out * channels_in].reshape(channels_out, channels_in).copy(), int(missing.value)
 
 
+class CProgramInspectRule(C.Structure):
+    """omx_program_inspect_rule (include/omx/program_inspect.h)"""
+    _fields_ = [("clip_level", C.c_float), ("clip_min_run", C.c_uint32), ("silence_level", C.c_float), ("silence_min_run", C.c_uint32),
+                ("dc_limit", C.c_float), ("correlation_min", C.c_float), ("flags", C.c_uint32)]
+
+
+class CProgramInspectInfo(C.Structure):
+    """omx_program_inspect_info (include/omx/program_inspect.h)"""
+    _fields_ = [("tile_frames", C.c_uint32), ("channels", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class CProgramInspectChannel(C.Structure):
+    """omx_program_inspect_channel (include/omx/program_inspect.h)"""
+    _fields_ = [("dc_sum", C.c_int64), ("nan_samples", C.c_uint64), ("clipped_samples", C.c_uint64), ("clip_runs", C.c_uint64),
+                ("longest_clip_run", C.c_uint64), ("longest_clip_start", C.c_uint64), ("open_clip_run", C.c_uint64), ("_pad", C.c_uint64)]
+
+
+class CProgramInspectPair(C.Structure):
+    """omx_program_inspect_pair (include/omx/program_inspect.h)"""
+    _fields_ = [("sum_ab", C.c_int64), ("sum_aa", C.c_uint64), ("sum_bb", C.c_uint64), ("a", C.c_uint32), ("b", C.c_uint32)]
+
+
+INSPECT_MAX_PAIRS = 4
+
+
+class CProgramInspectRecord(C.Structure):
+    """omx_program_inspect_record (include/omx/program_inspect.h)"""
+    _fields_ = [("frames", C.c_uint64), ("silent_frames", C.c_uint64), ("silent_runs", C.c_uint64), ("longest_silent_run", C.c_uint64),
+                ("longest_silent_start", C.c_uint64), ("leading_silence", C.c_uint64), ("trailing_silence", C.c_uint64),
+                ("channels", C.c_uint32), ("n_pairs", C.c_uint32), ("channel", CProgramInspectChannel * 8),
+                ("pair", CProgramInspectPair * INSPECT_MAX_PAIRS)]
+
+
+class CProgramInspectSummary(C.Structure):
+    """omx_program_inspect_summary (include/omx/program_inspect.h)"""
+    _fields_ = [("verdict", C.c_uint32), ("channels", C.c_uint32), ("n_pairs", C.c_uint32), ("_pad", C.c_uint32),
+                ("interior_silent_runs", C.c_uint64), ("dc_offset", C.c_float * 8), ("dc_offset_db", C.c_float * 8),
+                ("correlation", C.c_float * INSPECT_MAX_PAIRS), ("correlation_valid", C.c_uint32 * INSPECT_MAX_PAIRS)]
+
+
+INSPECT_INFO_DTYPE = np.dtype([("tile_frames", "<u4"), ("channels", "<u4"), ("_pad", "<u4", (2,))])
+INSPECT_CHANNEL_DTYPE = np.dtype([("dc_sum", "<i8"), ("nan_samples", "<u8"), ("clipped_samples", "<u8"), ("clip_runs", "<u8"),
+                                  ("longest_clip_run", "<u8"), ("longest_clip_start", "<u8"), ("open_clip_run", "<u8"), ("_pad", "<u8")])
+INSPECT_PAIR_DTYPE = np.dtype([("sum_ab", "<i8"), ("sum_aa", "<u8"), ("sum_bb", "<u8"), ("a", "<u4"), ("b", "<u4")])
+INSPECT_RECORD_DTYPE = np.dtype([("frames", "<u8"), ("silent_frames", "<u8"), ("silent_runs", "<u8"), ("longest_silent_run", "<u8"),
+                                 ("longest_silent_start", "<u8"), ("leading_silence", "<u8"), ("trailing_silence", "<u8"),
+                                 ("channels", "<u4"), ("n_pairs", "<u4"), ("channel", INSPECT_CHANNEL_DTYPE, (8,)),
+                                 ("pair", INSPECT_PAIR_DTYPE, (INSPECT_MAX_PAIRS,))])
+INSPECT_SUMMARY_DTYPE = np.dtype([("verdict", "<u4"), ("channels", "<u4"), ("n_pairs", "<u4"), ("_pad", "<u4"),
+                                  ("interior_silent_runs", "<u8"), ("dc_offset", "<f4", (8,)), ("dc_offset_db", "<f4", (8,)),
+                                  ("correlation", "<f4", (INSPECT_MAX_PAIRS,)), ("correlation_valid", "<u4", (INSPECT_MAX_PAIRS,))])
+assert C.sizeof(CProgramInspectRule) == 28 and C.sizeof(CProgramInspectInfo) == 16 and C.sizeof(CProgramInspectChannel) == 64
+assert C.sizeof(CProgramInspectPair) == 32 and C.sizeof(CProgramInspectRecord) == 704 and C.sizeof(CProgramInspectSummary) == 120
+assert INSPECT_INFO_DTYPE.itemsize == 16 and INSPECT_RECORD_DTYPE.itemsize == 704 and INSPECT_SUMMARY_DTYPE.itemsize == 120
+# omx_program_inspect_summary.verdict
+INSPECT_NAN, INSPECT_CLIPPED, INSPECT_DROPOUT, INSPECT_ALL_SILENT, INSPECT_DC, INSPECT_ANTIPHASE = 1, 2, 4, 8, 16, 32
+INSPECT_DB_FLOOR = -400.0
+
+
+@dataclass
+class InspectRule:
+    """omx_program_inspect_rule: a sample is hot at |x| >= clip_level and clip_min_run hot samples in a row are a clipping run; a frame
+    is quiet when every channel has |x| <= silence_level and silence_min_run quiet frames in a row are a silent run; the summary flags
+    a DC offset above dc_limit and a pair whose correlation lies below correlation_min.  The defaults are the header's."""
+    clip_level: float = 0.99996948
+    clip_min_run: int = 3
+    silence_level: float = 0.0
+    silence_min_run: int = 480
+    dc_limit: float = 1e-3
+    correlation_min: float = -0.2
+    flags: int = 0
+
+    def to_c(self) -> CProgramInspectRule:
+        return CProgramInspectRule(self.clip_level, self.clip_min_run, self.silence_level, self.silence_min_run, self.dc_limit,
+                                   self.correlation_min, self.flags)
+
+
+def inspect_rule_default(api: Api) -> InspectRule:
+    """The header's defaults as the library fills them (omx_program_inspect_rule_default).  Needs no device."""
+    c = CProgramInspectRule()
+    api.check(api.fn("program_inspect_rule_default", C.c_int, [C.c_void_p])(C.byref(c)))
+    return InspectRule(c.clip_level, c.clip_min_run, c.silence_level, c.silence_min_run, c.dc_limit, c.correlation_min, c.flags)
+
+
+def inspect_plan(api: Api, channels: int) -> np.ndarray:
+    """The plan of a channel count (omx_program_inspect_plan) as an INSPECT_INFO_DTYPE scalar: the main kernel's tile in frames.  Needs
+    no device."""
+    out = np.zeros((1,), INSPECT_INFO_DTYPE)
+    api.check(api.fn("program_inspect_plan", C.c_int, [C.c_uint32, C.c_void_p])(channels, out.ctypes.data))
+    return out[0]
+
+
+def inspect_summarize(api: Api, rule: InspectRule, record: np.ndarray) -> np.ndarray:
+    """The figures a person reads from one INSPECT_RECORD_DTYPE record (omx_program_inspect_summarize) as an INSPECT_SUMMARY_DTYPE
+    scalar: DC offsets, pair correlations, interior silent runs and the verdict bits (INSPECT_*).  Needs no device."""
+    rec = np.ascontiguousarray(np.asarray(record, INSPECT_RECORD_DTYPE).reshape(1))
+    out, c = np.zeros((1,), INSPECT_SUMMARY_DTYPE), rule.to_c()
+    api.check(api.fn("program_inspect_summarize", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])(C.byref(c), rec.ctypes.data, out.ctypes.data))
+    return out[0]
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -863,5 +964,40 @@ class ProgramLoudnessBank:
         """One stream's record of the last remix call as a REMIX_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), REMIX_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_remixed", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_inspect.h
+    def configure_inspect(self, rule: InspectRule, channels: int, pairs: Sequence[Sequence[int]] = ()):
+        """Set the inspector's rule, the channel count of the PCM it takes and up to INSPECT_MAX_PAIRS channel pairs (a, b) whose
+        correlation it keeps; allocates its records.  Only while no stream of the inspector holds frames: a new bank, or after
+        reset_inspect() of every stream."""
+        c = rule.to_c()
+        pr = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.uint32).reshape(-1, 2))
+        self.api.check(self.api.fn("program_loudness_bank_inspect_configure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32])(
+            self._h, C.byref(c), channels, pr.ctypes.data if pr.size else None, pr.shape[0]))
+
+    def reset_inspect(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the inspector start over with a zero record (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_inspect_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def inspect(self, d_in: int, frames_capacity: int, frames: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels]) into the running record of stream s, on
+        `stream`; d_in is only read.  Returns the device pointer to omx_program_inspect_record[n_streams] (INSPECT_RECORD_DTYPE): the
+        records run since the stream's reset and have the same bytes however the programme is cut into calls."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_inspect", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(stream or 0),
+                         C.byref(out)))
+        return out.value or 0
+
+    def fetch_inspected(self, stream_index: int) -> np.ndarray:
+        """One stream's running record as an INSPECT_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), INSPECT_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_inspected", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
