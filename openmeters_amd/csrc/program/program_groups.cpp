@@ -9,10 +9,9 @@ namespace omx {
 int ProgramLoudnessBank::measure_groups(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups,
                                         uint64_t n_groups, hipStream_t stream, const omx_program_loudness_record** d_records) {
     if (n_groups == 0) return OMX_NONE;
-    if (!groups || (!members && n_members > 0) || n_groups > 0x7FFFFFFFull || n_members > 0x7FFFFFFFull) {
-        set_last_error("program loudness measure_groups: null members or groups (or more than 2^31 - 1 of them)");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "measure_groups";
+    if (!groups || (!members && n_members > 0) || n_groups > 0x7FFFFFFFull || n_members > 0x7FFFFFFFull)
+        return pl_refuse(who, "null members or groups (or more than 2^31 - 1 of them)");
     // ---- the members, resolved; before[m] of member m in 64 bits for the groups' own counts
     const size_t groups_at = (size_t)n_members * sizeof(PgMember);
     h_group_tables_.resize(groups_at + (size_t)n_groups * sizeof(PgGroup));
@@ -27,10 +26,8 @@ int ProgramLoudnessBank::measure_groups(const omx_program_interval* members, uin
     for (uint64_t i = 0; i < n_members; ++i) {
         const omx_program_interval& in = members[i];
         if (in.stream >= n_streams_ || in.first_segment > h_meta_[in.stream].segments ||
-            (in.segment_count != OMX_PROGRAM_TO_END && in.segment_count > h_meta_[in.stream].segments - in.first_segment)) {
-            set_last_error("program loudness measure_groups: stream index out of range or member outside the stored segments");
-            return OMX_ERR_INVALID;
-        }
+            (in.segment_count != OMX_PROGRAM_TO_END && in.segment_count > h_meta_[in.stream].segments - in.first_segment))
+            return pl_refuse(who, "stream index out of range or member outside the stored segments");
         const uint64_t segments = h_meta_[in.stream].segments;
         const uint64_t n = in.segment_count == OMX_PROGRAM_TO_END ? segments - in.first_segment : in.segment_count;
         partial = partial || in.first_segment != 0 || n != segments;
@@ -41,15 +38,9 @@ int ProgramLoudnessBank::measure_groups(const omx_program_interval* members, uin
     }
     for (uint64_t k = 0; k < n_groups; ++k) {
         const omx_program_group& g = groups[k];
-        if (g.first_member > n_members || g.member_count > n_members - g.first_member) {
-            set_last_error("program loudness measure_groups: group range outside the member table");
-            return OMX_ERR_INVALID;
-        }
+        if (g.first_member > n_members || g.member_count > n_members - g.first_member) return pl_refuse(who, "group range outside the member table");
         const uint64_t lo = g.first_member, hi = g.first_member + g.member_count;
-        if (g_before[hi] - g_before[lo] > 0xFFFFFFFFull) {
-            set_last_error("program loudness measure_groups: more than 2^32 - 1 gating blocks in a group");
-            return OMX_ERR_INVALID;
-        }
+        if (g_before[hi] - g_before[lo] > 0xFFFFFFFFull) return pl_refuse(who, "more than 2^32 - 1 gating blocks in a group");
         const uint64_t segments = seg_before[hi] - seg_before[lo];
         const uint64_t st_blocks = s_before[hi] - s_before[lo];
         const bool stage = staging && st_blocks >= kPgStageMin && staged + st_blocks <= kPgStageMax;
@@ -91,10 +82,7 @@ int ProgramLoudnessBank::measure_groups(const omx_program_interval* members, uin
 int ProgramLoudnessBank::fetch_groups(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups,
                                       uint64_t n_groups, omx_program_loudness_record* dst) {
     if (n_groups == 0) return OMX_NONE;
-    if (!dst) {
-        set_last_error("program loudness fetch_groups: null records");
-        return OMX_ERR_INVALID;
-    }
+    if (!dst) return pl_refuse("fetch_groups", "null records");
     const int rc = measure_groups(members, n_members, groups, n_groups, last_stream_, nullptr);
     if (rc < 0) return rc;
     copy_out(dst, group_records_.ptr, (size_t)n_groups * sizeof(*dst), false, last_stream_);

@@ -50,14 +50,8 @@ int ProgramLoudnessBank::bounded_refusal(const char* what) const {
 }
 
 int ProgramLoudnessBank::fetch_histogram(uint64_t stream_index, omx_program_histogram* dst) {
-    if (!bounded_) {
-        set_last_error("program loudness fetch_histogram: the bank stores segments, not histograms");
-        return OMX_ERR_INVALID;
-    }
-    if (stream_index >= n_streams_) {
-        set_last_error("program loudness fetch_histogram: stream index out of range");
-        return OMX_ERR_INVALID;
-    }
+    if (!bounded_) return pl_refuse("fetch_histogram", "the bank stores segments, not histograms");
+    if (stream_index >= n_streams_) return pl_refuse("fetch_histogram", "stream index out of range");
     copy_out(dst, hist_.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

@@ -8,13 +8,6 @@ namespace omx {
 
 namespace {
 
-int in_refuse(const char* who, const char* why) {
-    set_last_error(std::string("program loudness ") + who + ": " + why);
-    return OMX_ERR_INVALID;
-}
-
-bool in_channels_ok(uint32_t c) { return c >= 1 && c <= OMX_MAX_CHANNELS; }
-
 bool in_rule_valid(const omx_program_inspect_rule* r) {
     return r && std::isfinite(r->clip_level) && r->clip_level > 0.0f && r->clip_min_run >= 1 && r->clip_min_run <= OMX_INSPECT_MAX_CLIP_MIN_RUN &&
            std::isfinite(r->silence_level) && r->silence_level >= 0.0f && r->silence_min_run >= 1 &&
@@ -29,7 +22,7 @@ const char* kBadRule =
 }  // namespace
 
 int in_rule_default(omx_program_inspect_rule* rule) {
-    if (!rule) return in_refuse("inspect rule_default", "null rule");
+    if (!rule) return pl_refuse("inspect rule_default", "null rule");
     omx_program_inspect_rule out{};
     out.clip_level = OMX_INSPECT_DEFAULT_CLIP_LEVEL;
     out.clip_min_run = OMX_INSPECT_DEFAULT_CLIP_MIN_RUN;
@@ -43,8 +36,8 @@ int in_rule_default(omx_program_inspect_rule* rule) {
 }
 
 int in_plan(uint32_t channels, omx_program_inspect_info* info) {
-    if (!info) return in_refuse("inspect plan", "null info");
-    if (!in_channels_ok(channels)) return in_refuse("inspect plan", "channels outside 1 .. 8");
+    if (!info) return pl_refuse("inspect plan", "null info");
+    if (!pl_channels_ok(channels)) return pl_refuse("inspect plan", "channels outside 1 .. 8");
     omx_program_inspect_info out{};
     out.tile_frames = in_tile_frames(channels);
     out.channels = channels;
@@ -54,10 +47,10 @@ int in_plan(uint32_t channels, omx_program_inspect_info* info) {
 
 int in_summarize(const omx_program_inspect_rule* rule, const omx_program_inspect_record* record, omx_program_inspect_summary* summary) {
     const char* who = "inspect summarize";
-    if (!record || !summary) return in_refuse(who, "null pointer");
-    if (!in_rule_valid(rule)) return in_refuse(who, kBadRule);
-    if (!in_channels_ok(record->channels)) return in_refuse(who, "record->channels outside 1 .. 8");
-    if (record->n_pairs > OMX_INSPECT_MAX_PAIRS) return in_refuse(who, "record->n_pairs above OMX_INSPECT_MAX_PAIRS");
+    if (!record || !summary) return pl_refuse(who, "null pointer");
+    if (!in_rule_valid(rule)) return pl_refuse(who, kBadRule);
+    if (!pl_channels_ok(record->channels)) return pl_refuse(who, "record->channels outside 1 .. 8");
+    if (record->n_pairs > OMX_INSPECT_MAX_PAIRS) return pl_refuse(who, "record->n_pairs above OMX_INSPECT_MAX_PAIRS");
     omx_program_inspect_summary out{};
     out.channels = record->channels;
     out.n_pairs = record->n_pairs;
@@ -96,16 +89,16 @@ int in_summarize(const omx_program_inspect_rule* rule, const omx_program_inspect
 
 int ProgramLoudnessBank::inspect_configure(const omx_program_inspect_rule* rule, uint32_t channels, const uint32_t* pairs, uint32_t n_pairs) {
     const char* who = "inspect_configure";
-    if (!in_rule_valid(rule)) return in_refuse(who, kBadRule);
-    if (!in_channels_ok(channels)) return in_refuse(who, "channels outside 1 .. 8");
-    if (n_pairs > OMX_INSPECT_MAX_PAIRS) return in_refuse(who, "n_pairs above OMX_INSPECT_MAX_PAIRS");
-    if (n_pairs && !pairs) return in_refuse(who, "null pairs");
+    if (!in_rule_valid(rule)) return pl_refuse(who, kBadRule);
+    if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
+    if (n_pairs > OMX_INSPECT_MAX_PAIRS) return pl_refuse(who, "n_pairs above OMX_INSPECT_MAX_PAIRS");
+    if (n_pairs && !pairs) return pl_refuse(who, "null pairs");
     for (uint32_t p = 0; p < n_pairs; ++p)
         if (pairs[2 * p] >= channels || pairs[2 * p + 1] >= channels || pairs[2 * p] == pairs[2 * p + 1])
-            return in_refuse(who, "a pair index at or above channels, or a pair of one channel");
+            return pl_refuse(who, "a pair index at or above channels, or a pair of one channel");
     if (inspector_)
         for (const uint64_t n : inspector_->h_frames)
-            if (n != 0) return in_refuse(who, "a stream of the inspector holds frames (reset every stream first)");
+            if (n != 0) return pl_refuse(who, "a stream of the inspector holds frames (reset every stream first)");
     if (inspector_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
     auto in = inspector_ ? std::move(inspector_) : std::make_unique<ProgramInspector>();
     in->rule = *rule;
@@ -147,14 +140,14 @@ InArgs ProgramLoudnessBank::inspect_args() const {
 }
 
 int ProgramLoudnessBank::inspect_reset(const uint8_t* reset_mask) {
-    if (!inspector_) return in_refuse("inspect_reset", "the inspector is not configured (omx_program_loudness_bank_inspect_configure)");
+    if (!inspector_) return pl_refuse("inspect_reset", "the inspector is not configured (omx_program_loudness_bank_inspect_configure)");
     ProgramInspector& in = *inspector_;
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const bool clear = !reset_mask || reset_mask[s];
         if (clear) in.h_frames[s] = 0;
         in.h_call[s] = clear ? 1u : 0u;
     }
-    in.staging.upload(in.h_call.data(), (size_t)n_streams_ * sizeof(uint32_t), in.call.ptr, last_stream_);
+    pl_upload_table(in.staging, in.h_call, in.call.ptr, last_stream_);
     launch_in_reset(inspect_args(), last_stream_);
     OMX_HIP(hipGetLastError());
     return OMX_NONE;
@@ -164,19 +157,19 @@ int ProgramLoudnessBank::inspect_reset(const uint8_t* reset_mask) {
 int ProgramLoudnessBank::inspect(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
                                  const omx_program_inspect_record** d_inspected) {
     const char* who = "inspect";
-    if (!inspector_) return in_refuse(who, "the inspector is not configured (omx_program_loudness_bank_inspect_configure)");
+    if (!inspector_) return pl_refuse(who, "the inspector is not configured (omx_program_loudness_bank_inspect_configure)");
     ProgramInspector& in = *inspector_;
-    if (frames_capacity > 0xFFFFFFFFull) return in_refuse(who, "frames_capacity beyond 2^32 - 1");
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
     uint32_t max_frames = 0;
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return in_refuse(who, "frames[s] > frames_capacity");
-        if (in.h_frames[s] + f > 0xFFFFFFFFull) return in_refuse(who, "a stream would hold more than 2^32 - 1 frames since its reset");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
+        if (in.h_frames[s] + f > 0xFFFFFFFFull) return pl_refuse(who, "a stream would hold more than 2^32 - 1 frames since its reset");
         in.h_call[s] = (uint32_t)f;  // (host scratch only)
         max_frames = std::max(max_frames, (uint32_t)f);
     }
     const bool any = max_frames != 0;
-    if (any && !d_in) return in_refuse(who, "null pcm");
+    if (any && !d_in) return pl_refuse(who, "null pcm");
 
     last_stream_ = stream;
     if (any) {
@@ -184,7 +177,7 @@ int ProgramLoudnessBank::inspect(const float* d_in, uint64_t frames_capacity, co
         const uint64_t tiles = ((uint64_t)max_frames + tile - 1) / tile;
         in.runs.reserve((size_t)n_streams_ * tiles * (in.channels + 1));
         in.sums.reserve((size_t)n_streams_ * tiles * (2 * in.channels + 3 * in.n_pairs));
-        in.staging.upload(in.h_call.data(), (size_t)n_streams_ * sizeof(uint32_t), in.call.ptr, stream);
+        pl_upload_table(in.staging, in.h_call, in.call.ptr, stream);
         InArgs a = inspect_args();
         a.in = d_in;
         a.frames_capacity = frames_capacity;
@@ -201,7 +194,7 @@ int ProgramLoudnessBank::inspect(const float* d_in, uint64_t frames_capacity, co
 
 int ProgramLoudnessBank::fetch_inspected(uint64_t stream_index, omx_program_inspect_record* dst) {
     if (!inspector_ || stream_index >= n_streams_)
-        return in_refuse("fetch_inspected", "the inspector is not configured, or stream index out of range");
+        return pl_refuse("fetch_inspected", "the inspector is not configured, or stream index out of range");
     copy_out(dst, inspector_->records.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

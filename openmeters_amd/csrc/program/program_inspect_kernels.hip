@@ -33,16 +33,13 @@
 //   Templated on the channel count (eight instantiations; DESIGN.md lists their registers, LDS and scratch).
 //   Only vector loads and vector stores are used, no atomics at all.
 #include "program_inspect.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t in_to_aligned(const float* p) {  // floats up to the next 16-byte boundary
-    return ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2;
-}
 
 __device__ __forceinline__ InRuns in_identity() { return InRuns{0, 0, 0, 0, 0, 0, 0, 0}; }
 
@@ -181,7 +178,7 @@ __global__ __launch_bounds__(kInThreads) void in_main_kernel(InArgs a, uint32_t 
     // not hot, has no NaN and adds nothing to any sum; only the quiet predicate has to ask whether the frame exists.
     const float* src = a.in + ((uint64_t)s * a.frames_capacity + first) * C;
     const uint32_t n = nf * C;
-    const uint32_t peel = min(n, in_to_aligned(src));
+    const uint32_t peel = min(n, ps_to_aligned(src));
     const uint32_t shift = (4u - peel) & 3u;
     {
         const uint32_t nvec = (n - peel) >> 2, tail = (n - peel) & 3u;
@@ -426,13 +423,10 @@ __global__ __launch_bounds__(kInFoldMaxThreads) void in_fold_kernel(InArgs a, ui
 
 template <int C>
 void in_launch_tiles(const InArgs& a, hipStream_t stream) {
-    // a launch holds at most 65535 streams in y and fewer than 2^32 threads: slabs of streams, as rm_launch_tiles
-    const uint64_t tiles = std::max<uint64_t>(a.tiles, 1);
-    const uint64_t slab = std::max<uint64_t>(std::min<uint64_t>(65535, ((1ull << 24) - 1) / tiles), 1);
-    for (uint64_t base = 0; base < a.n_streams; base += slab) {
-        const dim3 grid((uint32_t)tiles, (uint32_t)std::min<uint64_t>(slab, a.n_streams - base));
-        hipLaunchKernelGGL((in_main_kernel<C>), grid, dim3(kInThreads), 0, stream, a, (uint32_t)base);
-    }
+    const uint32_t tiles = std::max<uint32_t>(a.tiles, 1);
+    for_stream_slabs(a.n_streams, tiles, [&](uint32_t base, uint32_t count) {
+        hipLaunchKernelGGL((in_main_kernel<C>), dim3(tiles, count), dim3(kInThreads), 0, stream, a, base);
+    });
 }
 
 }  // namespace

@@ -8,15 +8,6 @@ namespace omx {
 
 namespace {
 
-constexpr size_t kTruePeakTaps = 48;  // loudness/processor.rs:75
-
-float true_peak_coefficient(size_t j, size_t factor) {  // :79-84, as program_peaks.cpp
-    const double offset = (double)j - (double)kTruePeakTaps * 0.5;
-    const double window = 0.5 * (1.0 - std::cos(2.0 * M_PI * (double)j / (double)kTruePeakTaps));
-    const double x = offset * M_PI / (double)factor;
-    return (float)(window * std::sin(x) / x);
-}
-
 bool lm_rule_valid(const omx_program_limit_rule* rule) {
     if (!rule) return false;
     if (!std::isfinite(rule->ceiling_db) || rule->ceiling_db < -120.0f || rule->ceiling_db > 20.0f) return false;
@@ -24,23 +15,18 @@ bool lm_rule_valid(const omx_program_limit_rule* rule) {
     return rule->flags == 0;
 }
 
-int lm_refuse(const char* who, const char* why) {
-    set_last_error(std::string("program loudness ") + who + ": " + why);
-    return OMX_ERR_INVALID;
-}
-
 }  // namespace
 
 int ProgramLoudnessBank::limiter_configure(const omx_program_limit_rule* rule, uint32_t channels, float sample_rate) {
     if (!lm_rule_valid(rule))
-        return lm_refuse("limiter_configure", "bad limit rule (null, ceiling_db not finite or outside [-120, 20], attack_frames outside 1 .. 4096, "
+        return pl_refuse("limiter_configure", "bad limit rule (null, ceiling_db not finite or outside [-120, 20], attack_frames outside 1 .. 4096, "
                                               "release_hold_frames above 16384 or a flag set)");
-    if (channels == 0 || channels > OMX_MAX_CHANNELS) return lm_refuse("limiter_configure", "channels outside 1 .. 8");
+    if (!pl_channels_ok(channels)) return pl_refuse("limiter_configure", "channels outside 1 .. 8");
     const float rate = sanitize_sample_rate(sample_rate);
     if (rate < kPlMinRate) unsupported("programme loudness below 3364 Hz: the K-weighting filter has poles outside the unit circle");
     if (limiter_)
         for (const auto& m : limiter_->h_streams)
-            if (m.n != 0) return lm_refuse("limiter_configure", "a stream of the limiter holds frames (reset every stream first)");
+            if (m.n != 0) return pl_refuse("limiter_configure", "a stream of the limiter holds frames (reset every stream first)");
     if (limiter_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
     auto lim = limiter_ ? std::move(limiter_) : std::make_unique<ProgramLimiter>();
     lim->rule = *rule;
@@ -78,14 +64,12 @@ LmArgs ProgramLoudnessBank::limiter_args() const {
     a.records = lim.records.ptr;
     a.ring_x = lim.ring_x.ptr;
     a.ring_q = lim.ring_q.ptr;
-    for (size_t tap = 0; tap < 12; ++tap)
-        for (size_t phase = 0; phase < 3; ++phase) a.fir4[tap][phase] = true_peak_coefficient(tap * 4 + phase + 1, 4);
-    for (size_t tap = 0; tap < 24; ++tap) a.fir2[tap] = true_peak_coefficient(tap * 2 + 1, 2);
+    pl_true_peak_fir(a.fir4, a.fir2);
     return a;
 }
 
 int ProgramLoudnessBank::limiter_reset(const uint8_t* reset_mask) {
-    if (!limiter_) return lm_refuse("limiter_reset", "the limiter is not configured (omx_program_loudness_bank_limiter_configure)");
+    if (!limiter_) return pl_refuse("limiter_reset", "the limiter is not configured (omx_program_loudness_bank_limiter_configure)");
     ProgramLimiter& lim = *limiter_;
     for (uint32_t s = 0; s < n_streams_; ++s) {
         LmStreamCall c{};
@@ -95,7 +79,7 @@ int ProgramLoudnessBank::limiter_reset(const uint8_t* reset_mask) {
         }
         lim.h_calls[s] = c;
     }
-    lim.staging.upload(lim.h_calls.data(), (size_t)n_streams_ * sizeof(LmStreamCall), lim.calls.ptr, last_stream_);
+    pl_upload_table(lim.staging, lim.h_calls, lim.calls.ptr, last_stream_);
     const LmArgs a = limiter_args();
     launch_lm_begin(a, false, last_stream_);
     launch_lm_finish(a, last_stream_);
@@ -108,23 +92,24 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
                                        const uint8_t* flush_mask, const omx_program_gain_record* d_gains, uint64_t n_gains,
                                        const uint32_t* gain_of_stream, hipStream_t stream, const omx_program_limit_record** d_limited) {
     const char* who = "apply_limited";
-    if (!limiter_) return lm_refuse(who, "the limiter is not configured (omx_program_loudness_bank_limiter_configure)");
+    if (!limiter_) return pl_refuse(who, "the limiter is not configured (omx_program_loudness_bank_limiter_configure)");
     ProgramLimiter& lim = *limiter_;
-    if (frames_capacity > 0xFFFFFFFFull || out_capacity > 0xFFFFFFFFull) return lm_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
+    if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
+        return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     LmArgs a = limiter_args();
     bool any_in = false, any_out = false, named = false;
     std::vector<LmStreamCall>& calls = lim.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const ProgramLimiter::Mirror& m = lim.h_streams[s];
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return lm_refuse(who, "frames[s] > frames_capacity");
-        if (f != 0 && m.flushed) return lm_refuse(who, "frames for a flushed stream (reset it first)");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
+        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
         const uint64_t index = gain_of_stream ? gain_of_stream[s] : s;
-        if (index != OMX_PROGRAM_UNITY_GAIN && index >= n_gains) return lm_refuse(who, "gain index at or above n_gains");
+        if (index != OMX_PROGRAM_UNITY_GAIN && index >= n_gains) return pl_refuse(who, "gain index at or above n_gains");
         const bool flush = m.flushed || (flush_mask && flush_mask[s]);
         const uint64_t n_new = m.n + f;
         const uint64_t e_new = flush ? n_new : std::max<uint64_t>(m.e, n_new > a.latency ? n_new - a.latency : 0);
-        if (e_new - m.e > out_capacity) return lm_refuse(who, "a stream would emit more than out_capacity frames");
+        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
         LmStreamCall c{};
         c.n_old = m.n;
         c.frames = (uint32_t)f;
@@ -141,14 +126,12 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
         a.max_frames = std::max(a.max_frames, c.frames);
         a.max_emit = std::max(a.max_emit, c.emit);
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return lm_refuse(who, "null pcm");
-    if (named && !d_gains) return lm_refuse(who, "null gain records while a stream names one");
-    if (d_in && d_out) {  // out of place only: a tile would read what another has already written
-        const unsigned __int128 in_bytes = (unsigned __int128)n_streams_ * frames_capacity * a.channels * sizeof(float);
-        const unsigned __int128 out_bytes = (unsigned __int128)n_streams_ * out_capacity * a.channels * sizeof(float);
-        const unsigned __int128 lo_in = reinterpret_cast<uintptr_t>(d_in), lo_out = reinterpret_cast<uintptr_t>(d_out);
-        if (in_bytes != 0 && out_bytes != 0 && lo_in < lo_out + out_bytes && lo_out < lo_in + in_bytes) return lm_refuse(who, "d_in and d_out overlap");
-    }
+    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
+    if (named && !d_gains) return pl_refuse(who, "null gain records while a stream names one");
+    // out of place only: a tile would read what another has already written
+    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
+    if (d_in && d_out && pl_ranges_overlap(d_in, frame_bytes * frames_capacity, d_out, frame_bytes * out_capacity))
+        return pl_refuse(who, "d_in and d_out overlap");
 
     for (uint32_t s = 0; s < n_streams_; ++s) {
         ProgramLimiter::Mirror& m = lim.h_streams[s];
@@ -157,7 +140,7 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
         m.flushed = (calls[s].flags & kLmFlagFlush) != 0;
     }
     last_stream_ = stream;
-    lim.staging.upload(calls.data(), (size_t)n_streams_ * sizeof(LmStreamCall), lim.calls.ptr, stream);
+    pl_upload_table(lim.staging, calls, lim.calls.ptr, stream);
     a.in = d_in;
     a.out = d_out;
     a.frames_capacity = frames_capacity;
@@ -190,7 +173,7 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
 
 int ProgramLoudnessBank::fetch_limited(uint64_t stream_index, omx_program_limit_record* dst) {
     if (!limiter_ || stream_index >= n_streams_)
-        return lm_refuse("fetch_limited", "the limiter is not configured, or stream index out of range");
+        return pl_refuse("fetch_limited", "the limiter is not configured, or stream index out of range");
     copy_out(dst, limiter_->records.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

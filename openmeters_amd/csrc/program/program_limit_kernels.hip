@@ -22,15 +22,12 @@
 //   carry  : the newest LA frames of PCM and the newest W + A - 2 values of q into the rings, behind the apply pass that read them.
 //   Only vector loads, vector stores and vector atomics are used.
 #include "program_limit.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34, as program_peaks_kernels.hip
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 
 __device__ __forceinline__ float lm_x_at(const LmArgs& a, const LmStreamCall& call, uint32_t s, int64_t rel, uint32_t c) {
     if ((int64_t)call.n_old + rel < 0 || rel >= (int64_t)call.frames) return 0.0f;
@@ -82,9 +79,8 @@ __global__ __launch_bounds__(64) void lm_begin_kernel(LmArgs a, uint32_t whole_c
 __global__ __launch_bounds__(64) void lm_finish_kernel(LmArgs a) {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_streams) return;
-    const float p = a.records[s].out_sample_peak, e = a.records[s].min_envelope;
-    a.records[s].out_sample_peak_db = power_to_db(p * p, a.floor_db);
-    a.records[s].max_reduction_db = -power_to_db(e * e, a.floor_db);
+    a.records[s].out_sample_peak_db = ps_peak_db(a.records[s].out_sample_peak, a.floor_db);
+    a.records[s].max_reduction_db = -ps_peak_db(a.records[s].min_envelope, a.floor_db);
 }
 
 // ---- level
@@ -261,8 +257,9 @@ __global__ __launch_bounds__(256) void lm_smooth_kernel(LmArgs a, uint32_t n_til
 
 // ---- apply
 struct LmTally {
-    uint32_t over = 0, limited = 0;
-    float peak = 0.0f, low = 1.0f;
+    PsTally out;           // of the emitted samples
+    uint32_t limited = 0;  // frames with Gf < 1
+    float low = 1.0f;      // the smallest Gf
 };
 
 // float i of the stream's output row: frame f = i / channels of the call's emitted frames
@@ -270,9 +267,7 @@ __device__ __forceinline__ float lm_scaled(const LmArgs& a, const LmStreamCall& 
                                            uint32_t c, LmTally& t) {
     const float gf = env[f];
     const float y = lm_x_at(a, call, s, (int64_t)f - (int64_t)call.held, c) * (gain * gf);
-    const float m = fabsf(y);
-    t.over += m > 1.0f ? 1u : 0u;  // false for NaN, true for infinity
-    t.peak = fmaxf(t.peak, m);     // a NaN operand is ignored
+    t.out.take(y);
     if (c == 0) {
         t.limited += gf < 1.0f ? 1u : 0u;
         t.low = fminf(t.low, gf);
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(kLmApplyThreads) void lm_apply_kernel(LmArgs a, uin
     const uint64_t n = (uint64_t)call.emit * C;
     if (n == 0) return;
     float* out = a.out + (uint64_t)s * a.out_capacity * C;
-    const uint64_t to_aligned = ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) >> 2;
+    const uint64_t to_aligned = ps_to_aligned(out);
     const uint32_t peel = (uint32_t)(to_aligned < n ? to_aligned : n);
     const uint64_t nvec = (n - peel) >> 2, v0 = (uint64_t)tile * kLmApplyTileVecs;
     if (tile != 0 && v0 >= nvec) return;  // (uniform over the workgroup, as the return above: no thread is left at the barrier below)
@@ -322,32 +317,23 @@ __global__ __launch_bounds__(kLmApplyThreads) void lm_apply_kernel(LmArgs a, uin
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-        t.over += (uint32_t)__shfl_xor((int)t.over, d);
-        t.limited += (uint32_t)__shfl_xor((int)t.limited, d);
-        t.peak = fmaxf(t.peak, __shfl_xor(t.peak, d));
-        t.low = fminf(t.low, __shfl_xor(t.low, d));
+        t.out.fold_step(d);
+        ps_fold_step(t.limited, PsSum{}, d);
+        ps_fold_step(t.low, PsMin{}, d);
     }
-    __shared__ uint32_t s_over[kLmApplyThreads / 64], s_limited[kLmApplyThreads / 64];
-    __shared__ float s_peak[kLmApplyThreads / 64], s_low[kLmApplyThreads / 64];
-    if ((tid & 63u) == 0) {
-        s_over[tid >> 6] = t.over;
-        s_limited[tid >> 6] = t.limited;
-        s_peak[tid >> 6] = t.peak;
-        s_low[tid >> 6] = t.low;
-    }
-    __syncthreads();
+    // the two fields of its own go through the barrier of the sample tally's fold: posted in front of it, gathered behind it
+    __shared__ uint32_t s_limited[kLmApplyThreads / 64];
+    __shared__ float s_low[kLmApplyThreads / 64];
+    ps_fold_post(t.limited, s_limited);
+    ps_fold_post(t.low, s_low);
+    t.out.fold_waves<kLmApplyThreads>();
     if (tid == 0) {
-        for (uint32_t w = 1; w < kLmApplyThreads / 64; ++w) {
-            t.over += s_over[w];
-            t.limited += s_limited[w];
-            t.peak = fmaxf(t.peak, s_peak[w]);
-            t.low = fminf(t.low, s_low[w]);
-        }
+        ps_fold_gather<kLmApplyThreads>(t.limited, PsSum{}, s_limited);
+        ps_fold_gather<kLmApplyThreads>(t.low, PsMin{}, s_low);
         omx_program_limit_record* r = a.records + s;
-        if (t.over != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_over), (unsigned long long)t.over);
+        t.out.commit(r);
         if (t.limited != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->frames_limited), (unsigned long long)t.limited);
-        // bit patterns of non-negative floats order like the values; fmaxf / fminf never let a NaN in (and Gf is never one)
-        if (t.peak > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&r->out_sample_peak), __float_as_uint(t.peak));
+        // (the bit pattern of a non-negative float orders like the value; fminf never lets a NaN in, and Gf is never one)
         if (t.low < 1.0f) atomicMin(reinterpret_cast<unsigned int*>(&r->min_envelope), __float_as_uint(t.low));
     }
 }

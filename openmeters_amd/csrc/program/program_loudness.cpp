@@ -119,38 +119,26 @@ int ProgramLoudnessBank::reset(const uint8_t* reset_mask) {
 
 int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, const uint32_t* frames, const uint8_t* reset_mask,
                                  uint32_t channels_in, float sample_rate, const uint8_t positions[OMX_MAX_CHANNELS], hipStream_t stream) {
-    if (frames_capacity > 0xFFFFFFFFull) {
-        set_last_error("program loudness process: frames_capacity beyond 2^32 - 1");
-        return OMX_ERR_INVALID;
-    }
-    if (channels_in == 0 || channels_in > OMX_MAX_CHANNELS) {  // (a clamped count with the caller's stride would read the wrong samples)
-        set_last_error("program loudness process: channels outside 1 .. 8");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "process";
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
+    // (a clamped count with the caller's stride would read the wrong samples)
+    if (!pl_channels_ok(channels_in)) return pl_refuse(who, "channels outside 1 .. 8");
     const uint32_t channels = channels_in;
     const float rate = sanitize_sample_rate(sample_rate);
     if (rate < kPlMinRate) unsupported("programme loudness below 3364 Hz: the K-weighting filter has poles outside the unit circle");
     bool any = false, any_reset = false;
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) {
-            set_last_error("program loudness process: frames[s] > frames_capacity");
-            return OMX_ERR_INVALID;
-        }
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
         any = any || f != 0;
         any_reset = any_reset || (reset_mask && reset_mask[s]);
     }
-    if (any && !d_pcm) {
-        set_last_error("program loudness process: null pcm");
-        return OMX_ERR_INVALID;
-    }
+    if (any && !d_pcm) return pl_refuse(who, "null pcm");
     if (rate != rate_ || channels != channels_) {
         // a programme cannot change its rate or layout: refused unless every stream that has taken samples starts over in this call
         for (uint32_t s = 0; s < n_streams_; ++s)
-            if (h_meta_[s].frames != 0 && !(reset_mask && reset_mask[s])) {
-                set_last_error("program loudness process: sample rate / channel count changed while a programme is running (reset it in the same call)");
-                return OMX_ERR_INVALID;
-            }
+            if (h_meta_[s].frames != 0 && !(reset_mask && reset_mask[s]))
+                return pl_refuse(who, "sample rate / channel count changed while a programme is running (reset it in the same call)");
         if (any || rate_ == 0.0f) {  // (a bare reset keeps the rate the next call may confirm or change)
             set_rate(rate);
             channels_ = channels;
@@ -179,7 +167,7 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         max_new = std::max(max_new, c.n_new);
         taken = taken || c.frames != 0;
     }
-    call_staging_.upload(h_calls_.data(), (size_t)n_streams_ * sizeof(PlStreamCall), calls_.ptr, stream);
+    pl_upload_table(call_staging_, h_calls_, calls_.ptr, stream);
     dirty_ = true;
 
     PlArgs a{};
@@ -275,7 +263,7 @@ PlResultArgs ProgramLoudnessBank::result_args() const {
 
 int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_record** d_records) {
     last_stream_ = stream;
-    meta_staging_.upload(h_meta_.data(), (size_t)n_streams_ * sizeof(PlStreamMeta), meta_.ptr, stream);
+    pl_upload_table(meta_staging_, h_meta_, meta_.ptr, stream);
     if (bounded_) bounded_results(stream);
     else launch_pl_results(result_args(), stream);
     OMX_HIP(hipGetLastError());
@@ -285,10 +273,7 @@ int ProgramLoudnessBank::results(hipStream_t stream, const omx_program_loudness_
 }
 
 int ProgramLoudnessBank::fetch(uint64_t stream_index, omx_program_loudness_record* dst) {
-    if (stream_index >= n_streams_) {
-        set_last_error("program loudness fetch: stream index out of range");
-        return OMX_ERR_INVALID;
-    }
+    if (stream_index >= n_streams_) return pl_refuse("fetch", "stream index out of range");
     if (dirty_) results(last_stream_, nullptr);
     copy_out(dst, records_.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
@@ -296,10 +281,8 @@ int ProgramLoudnessBank::fetch(uint64_t stream_index, omx_program_loudness_recor
 
 int ProgramLoudnessBank::fetch_segments(uint64_t stream_index, uint64_t first, uint64_t count, double* dst) {
     if (bounded_) return bounded_refusal("fetch_segments");
-    if (stream_index >= n_streams_ || first > h_meta_[stream_index].segments || count > h_meta_[stream_index].segments - first) {
-        set_last_error("program loudness fetch_segments: range outside the stored segments");
-        return OMX_ERR_INVALID;
-    }
+    if (stream_index >= n_streams_ || first > h_meta_[stream_index].segments || count > h_meta_[stream_index].segments - first)
+        return pl_refuse("fetch_segments", "range outside the stored segments");
     if (count == 0) return OMX_NONE;
     copy_out(dst, segments_.ptr + stream_index * capacity_ + first, count * sizeof(double), false, last_stream_);
     return OMX_NONE;

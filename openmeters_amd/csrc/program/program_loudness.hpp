@@ -4,6 +4,7 @@
 #pragma once
 #include "../common.hpp"
 #include "../../../include/omx/program_loudness.h"
+#include "program_stage.hpp"
 #include "program_peaks.hpp"
 #include "program_timeline.hpp"
 #include "program_histogram.hpp"

@@ -17,8 +17,7 @@ bool pn_rule_valid(const omx_program_gain_rule* rule) {
 }
 
 int bad_rule(const char* who) {
-    set_last_error(std::string("program loudness ") + who + ": bad gain rule (null, a non-finite field in use, min_gain_db > max_gain_db or an unknown flag)");
-    return OMX_ERR_INVALID;
+    return pl_refuse(who, "bad gain rule (null, a non-finite field in use, min_gain_db > max_gain_db or an unknown flag)");
 }
 
 }  // namespace
@@ -54,14 +53,9 @@ int ProgramLoudnessBank::plan_group_gains(const omx_program_gain_rule* rule, con
 }
 
 int ProgramLoudnessBank::fetch_gains(uint64_t first, uint64_t count, omx_program_gain_record* dst) {
-    if (gains_planned_ == 0) {
-        set_last_error("program loudness fetch_gains: no plan yet (plan_gains / plan_group_gains)");
-        return OMX_ERR_INVALID;
-    }
-    if (first > gains_planned_ || count > gains_planned_ - first || (!dst && count != 0)) {
-        set_last_error("program loudness fetch_gains: range outside the last plan (or null records)");
-        return OMX_ERR_INVALID;
-    }
+    if (gains_planned_ == 0) return pl_refuse("fetch_gains", "no plan yet (plan_gains / plan_group_gains)");
+    if (first > gains_planned_ || count > gains_planned_ - first || (!dst && count != 0))
+        return pl_refuse("fetch_gains", "range outside the last plan (or null records)");
     if (count == 0) return OMX_NONE;
     copy_out(dst, gain_records_.ptr + first, (size_t)count * sizeof(*dst), false, last_stream_);
     return OMX_NONE;
@@ -71,54 +65,33 @@ int ProgramLoudnessBank::fetch_gains(uint64_t first, uint64_t count, omx_program
 int ProgramLoudnessBank::apply_gains(const float* d_in, float* d_out, uint64_t frames_capacity, const uint32_t* frames, uint32_t channels,
                                      const omx_program_gain_record* d_gains, uint64_t n_gains, const uint32_t* gain_of_stream,
                                      hipStream_t stream, const omx_program_apply_record** d_applied) {
-    if (frames_capacity > 0xFFFFFFFFull) {
-        set_last_error("program loudness apply_gains: frames_capacity beyond 2^32 - 1");
-        return OMX_ERR_INVALID;
-    }
-    if (channels == 0 || channels > OMX_MAX_CHANNELS) {
-        set_last_error("program loudness apply_gains: channels outside 1 .. 8");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "apply_gains";
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
+    if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
     bool any = false, named = false;
     uint64_t max_n = 0;
     h_apply_calls_.resize(n_streams_);  // (host scratch only: what the device holds is untouched until the upload below)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) {
-            set_last_error("program loudness apply_gains: frames[s] > frames_capacity");
-            return OMX_ERR_INVALID;
-        }
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
         const uint64_t index = gain_of_stream ? gain_of_stream[s] : s;  // (a bank of 2^32 - 1 streams and more does not exist: s is never the unity index)
-        if (index != OMX_PROGRAM_UNITY_GAIN && index >= n_gains) {
-            set_last_error("program loudness apply_gains: gain index at or above n_gains");
-            return OMX_ERR_INVALID;
-        }
+        if (index != OMX_PROGRAM_UNITY_GAIN && index >= n_gains) return pl_refuse(who, "gain index at or above n_gains");
         any = any || f != 0;
         named = named || index != OMX_PROGRAM_UNITY_GAIN;
         h_apply_calls_[s] = PnStreamCall{f * channels, (uint32_t)index, 0};
         max_n = std::max(max_n, f * channels);
     }
-    if (any && (!d_in || !d_out)) {
-        set_last_error("program loudness apply_gains: null pcm");
-        return OMX_ERR_INVALID;
-    }
-    if (named && !d_gains) {
-        set_last_error("program loudness apply_gains: null gain records while a stream names one");
-        return OMX_ERR_INVALID;
-    }
-    if (any && d_in != d_out) {  // in place is fine; any other overlap would let a tile read what another has already scaled
-        const unsigned __int128 bytes = (unsigned __int128)n_streams_ * frames_capacity * channels * sizeof(float);
-        const unsigned __int128 lo_in = reinterpret_cast<uintptr_t>(d_in), lo_out = reinterpret_cast<uintptr_t>(d_out);
-        if (lo_in < lo_out + bytes && lo_out < lo_in + bytes) {
-            set_last_error("program loudness apply_gains: d_in and d_out overlap without being the same buffer");
-            return OMX_ERR_INVALID;
-        }
-    }
+    if (any && (!d_in || !d_out)) return pl_refuse(who, "null pcm");
+    if (named && !d_gains) return pl_refuse(who, "null gain records while a stream names one");
+    // in place is fine; any other overlap would let a tile read what another has already scaled
+    const unsigned __int128 bytes = (unsigned __int128)n_streams_ * frames_capacity * channels * sizeof(float);
+    if (any && d_in != d_out && pl_ranges_overlap(d_in, bytes, d_out, bytes))
+        return pl_refuse(who, "d_in and d_out overlap without being the same buffer");
 
     last_stream_ = stream;
     apply_calls_.reserve(n_streams_);
     apply_records_.reserve(n_streams_);
-    apply_staging_.upload(h_apply_calls_.data(), (size_t)n_streams_ * sizeof(PnStreamCall), apply_calls_.ptr, stream);
+    pl_upload_table(apply_staging_, h_apply_calls_, apply_calls_.ptr, stream);
     PnApplyArgs a{};
     a.in = d_in;
     a.out = d_out;
@@ -143,10 +116,7 @@ int ProgramLoudnessBank::apply_gains(const float* d_in, float* d_out, uint64_t f
 }
 
 int ProgramLoudnessBank::fetch_applied(uint64_t stream_index, omx_program_apply_record* dst) {
-    if (!applied_ || stream_index >= n_streams_) {
-        set_last_error("program loudness fetch_applied: no apply_gains call yet, or stream index out of range");
-        return OMX_ERR_INVALID;
-    }
+    if (!applied_ || stream_index >= n_streams_) return pl_refuse("fetch_applied", "no apply_gains call yet, or stream index out of range");
     copy_out(dst, apply_records_.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

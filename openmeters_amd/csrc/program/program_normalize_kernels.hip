@@ -19,15 +19,12 @@
 //   Only vector loads, vector stores and vector atomics are used.
 #include "program_gain_device.hpp"
 #include "program_normalize.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34, as program_peaks_kernels.hip
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 
 __global__ __launch_bounds__(64) void pn_plan_kernel(omx_program_gain_rule rule, const omx_program_loudness_record* records,
                                                       omx_program_gain_record* gains, uint32_t n, float floor_db) {
@@ -65,18 +62,11 @@ __global__ __launch_bounds__(64) void pn_begin_kernel(PnApplyArgs a) {
 __global__ __launch_bounds__(64) void pn_finish_kernel(PnApplyArgs a) {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_streams) return;
-    const float p = a.applied[s].out_sample_peak;
-    a.applied[s].out_sample_peak_db = power_to_db(p * p, a.floor_db);
-}
-
-__device__ __forceinline__ void pn_take(float y, uint32_t& over, float& peak) {
-    const float m = fabsf(y);
-    over += m > 1.0f ? 1u : 0u;  // false for NaN, true for infinity
-    peak = fmaxf(peak, m);       // a NaN operand is ignored
+    a.applied[s].out_sample_peak_db = ps_peak_db(a.applied[s].out_sample_peak, a.floor_db);
 }
 
 template <bool WIDE, bool NT>
-__device__ __forceinline__ void pn_body(const float* bi, float* bo, uint64_t v0, uint64_t nvec, float gain, uint32_t& over, float& peak) {
+__device__ __forceinline__ void pn_body(const float* bi, float* bo, uint64_t v0, uint64_t nvec, float gain, PsTally& tally) {
     const bool full = v0 + kPnTileVecs <= nvec;
     v4f x[kPnInFlight];
 #pragma unroll
@@ -93,10 +83,10 @@ __device__ __forceinline__ void pn_body(const float* bi, float* bo, uint64_t v0,
         const uint64_t v = v0 + k * kPnThreads + threadIdx.x;
         if (full || v < nvec) {
             const v4f y = x[k] * gain;
-            pn_take(y.x, over, peak);
-            pn_take(y.y, over, peak);
-            pn_take(y.z, over, peak);
-            pn_take(y.w, over, peak);
+            tally.take(y.x);
+            tally.take(y.y);
+            tally.take(y.z);
+            tally.take(y.w);
             v4f* q = reinterpret_cast<v4f*>(bo + 4 * v);
             if (NT) __builtin_nontemporal_store(y, q);
             else *q = y;
@@ -111,13 +101,12 @@ __global__ __launch_bounds__(kPnThreads) void pn_tile_kernel(PnApplyArgs a, uint
     if (n == 0) return;
     const float* in = a.in + (uint64_t)s * a.row;
     float* out = a.out + (uint64_t)s * a.row;
-    const uint64_t to_aligned = ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u)) & 15u) >> 2;
+    const uint64_t to_aligned = ps_to_aligned(out);
     const uint32_t peel = (uint32_t)(to_aligned < n ? to_aligned : n);
     const uint64_t nvec = (n - peel) >> 2, v0 = (uint64_t)t * kPnTileVecs;
     if (t != 0 && v0 >= nvec) return;  // (uniform over the workgroup, as the return above: no thread is left at the barrier below)
     const float gain = a.applied[s].gain;
-    uint32_t over = 0;
-    float peak = 0.0f;
+    PsTally tally;
     if (t == 0) {  // the floats outside the aligned body: threads 0 .. 2 the head, threads 4 .. 6 the tail
         const uint32_t tail = (uint32_t)((n - peel) & 3u);
         uint64_t i = n;
@@ -125,36 +114,17 @@ __global__ __launch_bounds__(kPnThreads) void pn_tile_kernel(PnApplyArgs a, uint
         else if (tid >= 4 && tid < 4 + tail) i = peel + 4 * nvec + (tid - 4);
         if (i < n) {
             const float y = in[i] * gain;
-            pn_take(y, over, peak);
+            tally.take(y);
             out[i] = y;
         }
     }
     if (v0 < nvec) {
         const float* bi = in + peel;
-        if ((reinterpret_cast<uintptr_t>(bi) & 15u) == 0) pn_body<true, NT>(bi, out + peel, v0, nvec, gain, over, peak);
-        else pn_body<false, NT>(bi, out + peel, v0, nvec, gain, over, peak);
+        if ((reinterpret_cast<uintptr_t>(bi) & 15u) == 0) pn_body<true, NT>(bi, out + peel, v0, nvec, gain, tally);
+        else pn_body<false, NT>(bi, out + peel, v0, nvec, gain, tally);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        over += (uint32_t)__shfl_xor((int)over, d);
-        peak = fmaxf(peak, __shfl_xor(peak, d));
-    }
-    __shared__ uint32_t s_over[kPnThreads / 64];
-    __shared__ float s_peak[kPnThreads / 64];
-    if ((tid & 63u) == 0) {
-        s_over[tid >> 6] = over;
-        s_peak[tid >> 6] = peak;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (uint32_t w = 1; w < kPnThreads / 64; ++w) {
-            over += s_over[w];
-            peak = fmaxf(peak, s_peak[w]);
-        }
-        omx_program_apply_record* r = a.applied + s;
-        if (over != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_over), (unsigned long long)over);
-        if (peak > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&r->out_sample_peak), __float_as_uint(peak));
-    }
+    tally.fold_workgroup<kPnThreads>();
+    if (tid == 0) tally.commit(a.applied + s);
 }
 
 }  // namespace
@@ -178,13 +148,11 @@ void launch_pn_finish(const PnApplyArgs& a, hipStream_t stream) {
 void launch_pn_tiles(const PnApplyArgs& a, uint64_t max_n, bool non_temporal, hipStream_t stream) {
     // tiles of the longest row (a row's body is at most max_n / 4 vectors; tile 0 exists for every row that brings a float)
     const uint64_t tiles = std::max<uint64_t>((max_n / 4 + kPnTileVecs - 1) / kPnTileVecs, 1);
-    // a launch holds at most 65535 streams in y and fewer than 2^32 threads: slabs of streams
-    const uint64_t slab = std::max<uint64_t>(std::min<uint64_t>(65535, ((1ull << 24) - 1) / tiles), 1);
-    for (uint64_t base = 0; base < a.n_streams; base += slab) {
-        const dim3 grid((uint32_t)tiles, (uint32_t)std::min<uint64_t>(slab, a.n_streams - base));
-        if (non_temporal) hipLaunchKernelGGL(pn_tile_kernel<true>, grid, dim3(kPnThreads), 0, stream, a, (uint32_t)base);
-        else hipLaunchKernelGGL(pn_tile_kernel<false>, grid, dim3(kPnThreads), 0, stream, a, (uint32_t)base);
-    }
+    for_stream_slabs(a.n_streams, tiles, [&](uint32_t base, uint32_t count) {
+        const dim3 grid((uint32_t)tiles, count);
+        if (non_temporal) hipLaunchKernelGGL(pn_tile_kernel<true>, grid, dim3(kPnThreads), 0, stream, a, base);
+        else hipLaunchKernelGGL(pn_tile_kernel<false>, grid, dim3(kPnThreads), 0, stream, a, base);
+    });
 }
 
 }  // namespace omx

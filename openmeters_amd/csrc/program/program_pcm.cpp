@@ -15,17 +15,6 @@ bool pc_rule_valid(const omx_program_export_rule* rule) {
     return rule->flags == 0;
 }
 
-int pc_refuse(const char* who, const char* why) {
-    set_last_error(std::string("program loudness ") + who + ": " + why);
-    return OMX_ERR_INVALID;
-}
-
-// [lo_a, lo_a + bytes_a) and [lo_b, lo_b + bytes_b) share a byte
-bool pc_overlap(const void* a, unsigned __int128 bytes_a, const void* b, unsigned __int128 bytes_b) {
-    const unsigned __int128 lo_a = reinterpret_cast<uintptr_t>(a), lo_b = reinterpret_cast<uintptr_t>(b);
-    return bytes_a != 0 && bytes_b != 0 && lo_a < lo_b + bytes_b && lo_b < lo_a + bytes_a;
-}
-
 }  // namespace
 
 // Everything is checked before anything is touched: a refused call leaves d_out as it was.
@@ -33,28 +22,29 @@ int ProgramLoudnessBank::import_pcm(const void* d_in, uint32_t format, float* d_
                                     uint32_t channels, hipStream_t stream) {
     const char* who = "import_pcm";
     const uint32_t bytes = pc_format_bytes(format);
-    if (bytes == 0) return pc_refuse(who, "unknown format");
-    if (frames_capacity > 0xFFFFFFFFull) return pc_refuse(who, "frames_capacity beyond 2^32 - 1");
-    if (channels == 0 || channels > OMX_MAX_CHANNELS) return pc_refuse(who, "channels outside 1 .. 8");
-    if (reinterpret_cast<uintptr_t>(d_in) & 3u) return pc_refuse(who, "d_in is not 4-byte aligned");
+    if (bytes == 0) return pl_refuse(who, "unknown format");
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
+    if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
+    if (reinterpret_cast<uintptr_t>(d_in) & 3u) return pl_refuse(who, "d_in is not 4-byte aligned");
     bool any = false;
     uint64_t max_n = 0;
     h_import_calls_.resize(n_streams_);  // (host scratch only)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return pc_refuse(who, "frames[s] > frames_capacity");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
         any = any || f != 0;
         h_import_calls_[s] = PcStreamCall{f * channels, 0, 0, 0, 0};
         max_n = std::max(max_n, f * channels);
     }
-    if (any && (!d_in || !d_out)) return pc_refuse(who, "null pcm");
+    if (any && (!d_in || !d_out)) return pl_refuse(who, "null pcm");
     const unsigned __int128 samples = (unsigned __int128)n_streams_ * frames_capacity * channels;
-    if (d_in && d_out && pc_overlap(d_in, samples * bytes, d_out, samples * sizeof(float))) return pc_refuse(who, "d_in and d_out overlap");
+    if (d_in && d_out && pl_ranges_overlap(d_in, samples * bytes, d_out, samples * sizeof(float)))
+        return pl_refuse(who, "d_in and d_out overlap");
     if (!any) return OMX_NONE;
 
     last_stream_ = stream;
     import_calls_.reserve(n_streams_);
-    import_staging_.upload(h_import_calls_.data(), (size_t)n_streams_ * sizeof(PcStreamCall), import_calls_.ptr, stream);
+    pl_upload_table(import_staging_, h_import_calls_, import_calls_.ptr, stream);
     PcArgs a{};
     a.in = d_in;
     a.out = d_out;
@@ -70,11 +60,11 @@ int ProgramLoudnessBank::import_pcm(const void* d_in, uint32_t format, float* d_
 
 int ProgramLoudnessBank::export_configure(const omx_program_export_rule* rule, uint32_t channels) {
     const char* who = "export_configure";
-    if (!pc_rule_valid(rule)) return pc_refuse(who, "bad export rule (null, an unknown format or dither, or a flag set)");
-    if (channels == 0 || channels > OMX_MAX_CHANNELS) return pc_refuse(who, "channels outside 1 .. 8");
+    if (!pc_rule_valid(rule)) return pl_refuse(who, "bad export rule (null, an unknown format or dither, or a flag set)");
+    if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
     if (exporter_)
         for (const uint64_t pos : exporter_->h_pos)
-            if (pos != 0) return pc_refuse(who, "a stream's export position is not 0 (reset every stream first)");
+            if (pos != 0) return pl_refuse(who, "a stream's export position is not 0 (reset every stream first)");
     if (exporter_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that writes the records may still be in flight)
     auto ex = exporter_ ? std::move(exporter_) : std::make_unique<ProgramExporter>();
     ex->rule = *rule;
@@ -90,7 +80,7 @@ int ProgramLoudnessBank::export_configure(const omx_program_export_rule* rule, u
 }
 
 int ProgramLoudnessBank::export_reset(const uint8_t* reset_mask) {
-    if (!exporter_) return pc_refuse("export_reset", "the export is not configured (omx_program_loudness_bank_export_configure)");
+    if (!exporter_) return pl_refuse("export_reset", "the export is not configured (omx_program_loudness_bank_export_configure)");
     ProgramExporter& ex = *exporter_;
     for (uint32_t s = 0; s < n_streams_; ++s) {
         PcStreamCall c{};
@@ -102,7 +92,7 @@ int ProgramLoudnessBank::export_reset(const uint8_t* reset_mask) {
         }
         ex.h_calls[s] = c;
     }
-    ex.staging.upload(ex.h_calls.data(), (size_t)n_streams_ * sizeof(PcStreamCall), ex.calls.ptr, last_stream_);
+    pl_upload_table(ex.staging, ex.h_calls, ex.calls.ptr, last_stream_);
     PcArgs a{};
     a.calls = ex.calls.ptr;
     a.records = ex.records.ptr;
@@ -120,27 +110,28 @@ int ProgramLoudnessBank::export_reset(const uint8_t* reset_mask) {
 int ProgramLoudnessBank::export_pcm(const float* d_in, void* d_out, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
                                     const omx_program_export_record** d_exported) {
     const char* who = "export_pcm";
-    if (!exporter_) return pc_refuse(who, "the export is not configured (omx_program_loudness_bank_export_configure)");
+    if (!exporter_) return pl_refuse(who, "the export is not configured (omx_program_loudness_bank_export_configure)");
     ProgramExporter& ex = *exporter_;
-    if (frames_capacity > 0xFFFFFFFFull) return pc_refuse(who, "frames_capacity beyond 2^32 - 1");
-    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return pc_refuse(who, "d_out is not 4-byte aligned");
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return pl_refuse(who, "d_out is not 4-byte aligned");
     const uint32_t bytes = pc_format_bytes(ex.rule.format), channels = ex.channels;
     bool any = false;
     uint64_t max_n = 0;
     for (uint32_t s = 0; s < n_streams_; ++s) {  // (host scratch only: the positions are committed below, after the last check)
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return pc_refuse(who, "frames[s] > frames_capacity");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
         any = any || f != 0;
         ex.h_calls[s] = PcStreamCall{f * channels, ex.h_pos[s], pc_stream_key(ex.rule.seed, s), 0, 0};
         max_n = std::max(max_n, f * channels);
     }
-    if (any && (!d_in || !d_out)) return pc_refuse(who, "null pcm");
+    if (any && (!d_in || !d_out)) return pl_refuse(who, "null pcm");
     const unsigned __int128 samples = (unsigned __int128)n_streams_ * frames_capacity * channels;
-    if (d_in && d_out && pc_overlap(d_in, samples * sizeof(float), d_out, samples * bytes)) return pc_refuse(who, "d_in and d_out overlap");
+    if (d_in && d_out && pl_ranges_overlap(d_in, samples * sizeof(float), d_out, samples * bytes))
+        return pl_refuse(who, "d_in and d_out overlap");
 
     for (uint32_t s = 0; s < n_streams_; ++s) ex.h_pos[s] += ex.h_calls[s].n / channels;
     last_stream_ = stream;
-    ex.staging.upload(ex.h_calls.data(), (size_t)n_streams_ * sizeof(PcStreamCall), ex.calls.ptr, stream);
+    pl_upload_table(ex.staging, ex.h_calls, ex.calls.ptr, stream);
     PcArgs a{};
     a.in = d_in;
     a.out = d_out;
@@ -162,7 +153,7 @@ int ProgramLoudnessBank::export_pcm(const float* d_in, void* d_out, uint64_t fra
 
 int ProgramLoudnessBank::fetch_exported(uint64_t stream_index, omx_program_export_record* dst) {
     if (!exporter_ || stream_index >= n_streams_)
-        return pc_refuse("fetch_exported", "the export is not configured, or stream index out of range");
+        return pl_refuse("fetch_exported", "the export is not configured, or stream index out of range");
     copy_out(dst, exporter_->records.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

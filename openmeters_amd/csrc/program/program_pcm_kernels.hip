@@ -26,16 +26,13 @@
 //             stream's record.  Sums of counts and a maximum of integers do not depend on arrival order.
 //   Only vector loads, vector stores and vector atomics are used.
 #include "program_pcm.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34, as program_peaks_kernels.hip
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 
 template <int BYTES>
 struct PcFormat;
@@ -212,7 +209,7 @@ __global__ __launch_bounds__(64) void pc_export_finish_kernel(PcArgs a) {
     if (s >= a.n_streams) return;
     const uint32_t bits = a.format == OMX_PCM_S16 ? 16u : a.format == OMX_PCM_S24 ? 24u : 32u;
     const float p = (float)((double)a.records[s].out_peak / (double)(1ull << (bits - 1)));
-    a.records[s].out_peak_db = power_to_db(p * p, a.floor_db);
+    a.records[s].out_peak_db = ps_peak_db(p, a.floor_db);
 }
 
 struct PcTally {
@@ -394,20 +391,19 @@ __global__ __launch_bounds__(kPcThreads) void pc_export_kernel(PcArgs a, uint32_
 
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-        tally.clipped += (uint32_t)__shfl_xor((int)tally.clipped, d);
-        tally.nans += (uint32_t)__shfl_xor((int)tally.nans, d);
-        const uint32_t other = (uint32_t)__shfl_xor((int)tally.peak, d);
-        tally.peak = other > tally.peak ? other : tally.peak;
+        ps_fold_step(tally.clipped, PsSum{}, d);
+        ps_fold_step(tally.nans, PsSum{}, d);
+        ps_fold_step(tally.peak, PsMax{}, d);
     }
-    __shared__ PcTally s_tally[kPcThreads / 64];
-    if ((tid & 63u) == 0) s_tally[tid >> 6] = tally;
+    __shared__ uint32_t s_clipped[kPcThreads / 64], s_nans[kPcThreads / 64], s_peak[kPcThreads / 64];
+    ps_fold_post(tally.clipped, s_clipped);
+    ps_fold_post(tally.nans, s_nans);
+    ps_fold_post(tally.peak, s_peak);
     __syncthreads();
     if (tid == 0) {
-        for (uint32_t w = 1; w < kPcThreads / 64; ++w) {
-            tally.clipped += s_tally[w].clipped;
-            tally.nans += s_tally[w].nans;
-            tally.peak = s_tally[w].peak > tally.peak ? s_tally[w].peak : tally.peak;
-        }
+        ps_fold_gather<kPcThreads>(tally.clipped, PsSum{}, s_clipped);
+        ps_fold_gather<kPcThreads>(tally.nans, PsSum{}, s_nans);
+        ps_fold_gather<kPcThreads>(tally.peak, PsMax{}, s_peak);
         omx_program_export_record* r = a.records + s;
         if (tally.clipped != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_clipped), (unsigned long long)tally.clipped);
         if (tally.nans != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_nan), (unsigned long long)tally.nans);
@@ -415,14 +411,11 @@ __global__ __launch_bounds__(kPcThreads) void pc_export_kernel(PcArgs a, uint32_
     }
 }
 
-// tiles of the longest row (its body is at most max_n / 16 threads' worth; tile 0 exists for every row that brings a sample); a
-// launch holds at most 65535 streams in y and fewer than 2^32 threads: slabs of streams
+// tiles of the longest row (its body is at most max_n / 16 threads' worth; tile 0 exists for every row that brings a sample)
 template <class Launch>
 void pc_slabs(uint64_t max_n, uint32_t n_streams, Launch&& launch) {
     const uint64_t tiles = std::max<uint64_t>((max_n + kPcTileSamples - 1) / kPcTileSamples, 1);
-    const uint64_t slab = std::max<uint64_t>(std::min<uint64_t>(65535, ((1ull << 24) - 1) / tiles), 1);
-    for (uint64_t base = 0; base < n_streams; base += slab)
-        launch(dim3((uint32_t)tiles, (uint32_t)std::min<uint64_t>(slab, n_streams - base)), (uint32_t)base);
+    for_stream_slabs(n_streams, tiles, [&](uint32_t base, uint32_t count) { launch(dim3((uint32_t)tiles, count), base); });
 }
 
 }  // namespace

@@ -4,25 +4,9 @@
 
 namespace omx {
 
-namespace {
-
-constexpr size_t kTruePeakTaps = 48;  // loudness/processor.rs:75
-
-float true_peak_coefficient(size_t j, size_t factor) {  // :79-84
-    const double offset = (double)j - (double)kTruePeakTaps * 0.5;
-    const double window = 0.5 * (1.0 - std::cos(2.0 * M_PI * (double)j / (double)kTruePeakTaps));
-    const double x = offset * M_PI / (double)factor;
-    return (float)(window * std::sin(x) / x);
-}
-
-}  // namespace
-
 int ProgramLoudnessBank::set_peaks(bool on) {
     for (uint32_t s = 0; s < n_streams_; ++s)
-        if (h_meta_[s].frames != 0) {
-            set_last_error("program loudness set_peaks: a stream holds samples (reset every stream first)");
-            return OMX_ERR_INVALID;
-        }
+        if (h_meta_[s].frames != 0) return pl_refuse("set_peaks", "a stream holds samples (reset every stream first)");
     if (on) {
         peak_records_.reserve(n_streams_);
         peak_delay_.reserve((size_t)n_streams_ * kPlSlots * kPkMaxDelay);
@@ -54,9 +38,7 @@ void ProgramLoudnessBank::measure_peaks(const float* d_pcm, uint64_t frames_capa
     p.calls = calls_.ptr;
     p.delay = peak_delay_.ptr;
     p.records = peak_records_.ptr;
-    for (size_t tap = 0; tap < 12; ++tap)
-        for (size_t phase = 0; phase < 3; ++phase) p.fir4[tap][phase] = true_peak_coefficient(tap * 4 + phase + 1, 4);
-    for (size_t tap = 0; tap < 24; ++tap) p.fir2[tap] = true_peak_coefficient(tap * 2 + 1, 2);
+    pl_true_peak_fir(p.fir4, p.fir2);
     if (p.n_tiles != 0) {
         peak_partials_.reserve((size_t)n_streams_ * channels_ * p.n_tiles);
         p.partials = peak_partials_.ptr;
@@ -66,24 +48,15 @@ void ProgramLoudnessBank::measure_peaks(const float* d_pcm, uint64_t frames_capa
 }
 
 int ProgramLoudnessBank::peaks(hipStream_t stream, const omx_program_peak_record** d_records) {
-    if (!peaks_on_) {
-        set_last_error("program loudness peaks: peaks are off (omx_program_loudness_bank_set_peaks)");
-        return OMX_ERR_INVALID;
-    }
+    if (!peaks_on_) return pl_refuse("peaks", "peaks are off (omx_program_loudness_bank_set_peaks)");
     last_stream_ = stream;
     *d_records = peak_records_.ptr;
     return OMX_NONE;
 }
 
 int ProgramLoudnessBank::fetch_peaks(uint64_t stream_index, omx_program_peak_record* dst) {
-    if (!peaks_on_) {
-        set_last_error("program loudness fetch_peaks: peaks are off (omx_program_loudness_bank_set_peaks)");
-        return OMX_ERR_INVALID;
-    }
-    if (stream_index >= n_streams_) {
-        set_last_error("program loudness fetch_peaks: stream index out of range");
-        return OMX_ERR_INVALID;
-    }
+    if (!peaks_on_) return pl_refuse("fetch_peaks", "peaks are off (omx_program_loudness_bank_set_peaks)");
+    if (stream_index >= n_streams_) return pl_refuse("fetch_peaks", "stream index out of range");
     copy_out(dst, peak_records_.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

@@ -21,6 +21,7 @@
 // Fold, one workgroup per stream, one wavefront per channel slot: the partials in tile order into the running record, the frame base
 // added, the delay line of the next call written, the record's dB fields and maxima rebuilt.
 #include "program_loudness.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
@@ -33,9 +34,6 @@ constexpr uint32_t kChanStride = (T + kHalo) / 16 * 17;    // dwords of one chan
 constexpr uint32_t kThreads = 256;
 static_assert(T == 64 * R && R == 16 && kHalo >= kPkMaxDelay - 1 && T % (4 * 64) == 0, "one wavefront per channel of a tile; pad per 16 frames");
 
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 __device__ __forceinline__ unsigned long long peak_key(float v, uint32_t frame) {
     return ((unsigned long long)__float_as_uint(v) << 32) | (unsigned long long)(0xFFFFFFFFu - frame);
 }

@@ -8,13 +8,6 @@ namespace omx {
 
 namespace {
 
-int rm_refuse(const char* who, const char* why) {
-    set_last_error(std::string("program loudness ") + who + ": " + why);
-    return OMX_ERR_INVALID;
-}
-
-bool rm_channels_ok(uint32_t c) { return c >= 1 && c <= OMX_MAX_CHANNELS; }
-
 bool rm_level_ok(float v) { return std::isfinite(v) && v >= 0.0f && v <= 2.0f; }
 
 // The term lists of one matrix [channels_out][channels_in]: the non-zero coefficients of every row, input channels in increasing order
@@ -39,8 +32,8 @@ RmMatrix rm_compact(const float* m, uint32_t channels_in, uint32_t channels_out)
 }  // namespace
 
 int rm_plan(uint32_t channels_in, uint32_t channels_out, omx_program_remix_info* info) {
-    if (!info) return rm_refuse("remix plan", "null info");
-    if (!rm_channels_ok(channels_in) || !rm_channels_ok(channels_out)) return rm_refuse("remix plan", "a channel count outside 1 .. 8");
+    if (!info) return pl_refuse("remix plan", "null info");
+    if (!pl_channels_ok(channels_in) || !pl_channels_ok(channels_out)) return pl_refuse("remix plan", "a channel count outside 1 .. 8");
     omx_program_remix_info out{};
     out.tile_frames = kRmThreads * rm_frames_per_thread(channels_in, channels_out);
     out.channels_in = channels_in;
@@ -52,12 +45,12 @@ int rm_plan(uint32_t channels_in, uint32_t channels_out, omx_program_remix_info*
 int rm_downmix(const omx_program_downmix_rule* rule, uint32_t channels_in, const uint8_t* positions_in, float* matrix, uint32_t* channels_out,
                uint8_t* positions_out) {
     const char* who = "remix downmix";
-    if (!rule || !positions_in || !matrix || !channels_out || !positions_out) return rm_refuse(who, "null pointer");
-    if (!rm_channels_ok(channels_in)) return rm_refuse(who, "channels_in outside 1 .. 8");
-    if (rule->kind != OMX_REMIX_KIND_STEREO && rule->kind != OMX_REMIX_KIND_MONO) return rm_refuse(who, "unknown kind");
-    if (rule->flags & ~OMX_REMIX_NORMALIZE) return rm_refuse(who, "unknown flag");
+    if (!rule || !positions_in || !matrix || !channels_out || !positions_out) return pl_refuse(who, "null pointer");
+    if (!pl_channels_ok(channels_in)) return pl_refuse(who, "channels_in outside 1 .. 8");
+    if (rule->kind != OMX_REMIX_KIND_STEREO && rule->kind != OMX_REMIX_KIND_MONO) return pl_refuse(who, "unknown kind");
+    if (rule->flags & ~OMX_REMIX_NORMALIZE) return pl_refuse(who, "unknown flag");
     if (!rm_level_ok(rule->center_level) || !rm_level_ok(rule->surround_level) || !rm_level_ok(rule->lfe_level))
-        return rm_refuse(who, "a level that is not finite or lies outside [0, 2]");
+        return pl_refuse(who, "a level that is not finite or lies outside [0, 2]");
     const float c = rule->center_level, s = rule->surround_level, l = rule->lfe_level;
     float wl[OMX_MAX_CHANNELS], wr[OMX_MAX_CHANNELS];
     for (uint32_t i = 0; i < channels_in; ++i) {
@@ -111,8 +104,8 @@ int rm_downmix(const omx_program_downmix_rule* rule, uint32_t channels_in, const
 int rm_select(uint32_t channels_in, const uint8_t* positions_in, uint32_t channels_out, const uint8_t* positions_out, float* matrix,
               uint32_t* missing_mask) {
     const char* who = "remix select";
-    if (!positions_in || !positions_out || !matrix || !missing_mask) return rm_refuse(who, "null pointer");
-    if (!rm_channels_ok(channels_in) || !rm_channels_ok(channels_out)) return rm_refuse(who, "a channel count outside 1 .. 8");
+    if (!positions_in || !positions_out || !matrix || !missing_mask) return pl_refuse(who, "null pointer");
+    if (!pl_channels_ok(channels_in) || !pl_channels_ok(channels_out)) return pl_refuse(who, "a channel count outside 1 .. 8");
     uint32_t missing = 0;
     for (uint32_t o = 0; o < channels_out; ++o) {
         bool found = false;
@@ -129,12 +122,12 @@ int rm_select(uint32_t channels_in, const uint8_t* positions_in, uint32_t channe
 
 int ProgramLoudnessBank::remix_configure(uint32_t channels_in, uint32_t channels_out, const float* matrices, uint32_t n_matrices) {
     const char* who = "remix_configure";
-    if (!rm_channels_ok(channels_in) || !rm_channels_ok(channels_out)) return rm_refuse(who, "a channel count outside 1 .. 8");
-    if (!matrices) return rm_refuse(who, "null table");
-    if (n_matrices == 0 || n_matrices > OMX_REMIX_MAX_MATRICES) return rm_refuse(who, "n_matrices 0 or above OMX_REMIX_MAX_MATRICES");
+    if (!pl_channels_ok(channels_in) || !pl_channels_ok(channels_out)) return pl_refuse(who, "a channel count outside 1 .. 8");
+    if (!matrices) return pl_refuse(who, "null table");
+    if (n_matrices == 0 || n_matrices > OMX_REMIX_MAX_MATRICES) return pl_refuse(who, "n_matrices 0 or above OMX_REMIX_MAX_MATRICES");
     const size_t per = (size_t)channels_in * channels_out;
     for (size_t i = 0; i < per * n_matrices; ++i)
-        if (!std::isfinite(matrices[i])) return rm_refuse(who, "a coefficient that is not finite");
+        if (!std::isfinite(matrices[i])) return pl_refuse(who, "a coefficient that is not finite");
     std::vector<RmMatrix> compact(n_matrices);
     std::vector<uint32_t> terms(n_matrices);
     for (uint32_t k = 0; k < n_matrices; ++k) {
@@ -155,7 +148,7 @@ int ProgramLoudnessBank::remix_configure(uint32_t channels_in, uint32_t channels
     remix_ = std::move(rm);  // (the earlier buffers are released here, behind the wait above)
     // the records of a call that brought nothing, so that fetch_remixed has something to say before the first call
     for (uint32_t s = 0; s < n_streams_; ++s) remix_->h_calls[s] = RmStreamCall{0, 0, remix_->h_terms[0], 0};
-    remix_->staging.upload(remix_->h_calls.data(), (size_t)n_streams_ * sizeof(RmStreamCall), remix_->calls.ptr, last_stream_);
+    pl_upload_table(remix_->staging, remix_->h_calls, remix_->calls.ptr, last_stream_);
     const RmArgs a = remix_args();
     launch_rm_begin(a, last_stream_);
     OMX_HIP(hipGetLastError());
@@ -180,30 +173,28 @@ RmArgs ProgramLoudnessBank::remix_args() const {
 int ProgramLoudnessBank::remix(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, const uint32_t* matrix_of_stream,
                                hipStream_t stream, const omx_program_remix_record** d_remixed) {
     const char* who = "remix";
-    if (!remix_) return rm_refuse(who, "the remix is not configured (omx_program_loudness_bank_remix_configure)");
+    if (!remix_) return pl_refuse(who, "the remix is not configured (omx_program_loudness_bank_remix_configure)");
     ProgramRemix& rm = *remix_;
-    if (frames_capacity > 0xFFFFFFFFull) return rm_refuse(who, "frames_capacity beyond 2^32 - 1");
+    if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
     RmArgs a = remix_args();
     std::vector<RmStreamCall>& calls = rm.h_calls;  // (host scratch only)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return rm_refuse(who, "frames[s] > frames_capacity");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
         const uint32_t m = matrix_of_stream ? matrix_of_stream[s] : 0u;
-        if (m >= rm.n_matrices) return rm_refuse(who, "matrix index out of range");
+        if (m >= rm.n_matrices) return pl_refuse(who, "matrix index out of range");
         calls[s] = RmStreamCall{(uint32_t)f, m, rm.h_terms[m], 0};
         a.max_frames = std::max(a.max_frames, (uint32_t)f);
     }
     const bool any = a.max_frames != 0;
-    if (any && (!d_in || !d_out)) return rm_refuse(who, "null pcm");
-    if (d_in && d_out) {  // out of place only: a tile would read what another has already written
-        const unsigned __int128 in_bytes = (unsigned __int128)n_streams_ * frames_capacity * a.channels_in * sizeof(float);
-        const unsigned __int128 out_bytes = (unsigned __int128)n_streams_ * frames_capacity * a.channels_out * sizeof(float);
-        const unsigned __int128 lo_in = reinterpret_cast<uintptr_t>(d_in), lo_out = reinterpret_cast<uintptr_t>(d_out);
-        if (in_bytes != 0 && out_bytes != 0 && lo_in < lo_out + out_bytes && lo_out < lo_in + in_bytes) return rm_refuse(who, "d_in and d_out overlap");
-    }
+    if (any && (!d_in || !d_out)) return pl_refuse(who, "null pcm");
+    // out of place only: a tile would read what another has already written
+    const unsigned __int128 row_bytes = (unsigned __int128)n_streams_ * frames_capacity * sizeof(float);
+    if (d_in && d_out && pl_ranges_overlap(d_in, row_bytes * a.channels_in, d_out, row_bytes * a.channels_out))
+        return pl_refuse(who, "d_in and d_out overlap");
 
     last_stream_ = stream;
-    rm.staging.upload(calls.data(), (size_t)n_streams_ * sizeof(RmStreamCall), rm.calls.ptr, stream);
+    pl_upload_table(rm.staging, calls, rm.calls.ptr, stream);
     a.in = d_in;
     a.out = d_out;
     a.frames_capacity = frames_capacity;
@@ -216,7 +207,7 @@ int ProgramLoudnessBank::remix(const float* d_in, uint64_t frames_capacity, cons
 }
 
 int ProgramLoudnessBank::fetch_remixed(uint64_t stream_index, omx_program_remix_record* dst) {
-    if (!remix_ || stream_index >= n_streams_) return rm_refuse("fetch_remixed", "the remix is not configured, or stream index out of range");
+    if (!remix_ || stream_index >= n_streams_) return pl_refuse("fetch_remixed", "the remix is not configured, or stream index out of range");
     copy_out(dst, remix_->records.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

@@ -22,22 +22,19 @@
 //     out    out[f][o] goes to s_y[f * SO + o]; SO = channels_out, but channels_out + 1 for 4 and 8 channels (the dword stores of a
 //            group would collide 4 and 8 ways; with 2 or 6 they collide 2 ways, which a ds_write_b32 absorbs).  The tile's output is
 //            one contiguous run of d_out and leaves like the input came: head and tail by dword, the body in aligned 16-byte stores.
-//     reduce exactly pn_tile_kernel's scheme (program_normalize_kernels.hip): count and maximum per thread, six shuffle steps, four
-//            wavefronts through LDS, at most one atomicAdd (u64) and one atomicMax (bit pattern) per workgroup.
+//     reduce PsTally (program_stage_device.hpp): count and maximum per thread, six shuffle steps, four wavefronts through LDS, at
+//            most one atomicAdd (u64) and one atomicMax (bit pattern) per workgroup.
 //   Templated on channels_in (and the frames per thread that go with it), not on channels_out: the input staging divides every
 //   float's index by the channel count, which has to be a constant to be cheap, while channels_out only bounds a uniform loop and
 //   strides the output staging (a shift for 4 and 8).  Fourteen instantiations; DESIGN.md lists their registers, LDS and scratch.
 //   Only vector loads, vector stores and vector atomics are used.
 #include "program_remix.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34, as program_peaks_kernels.hip
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 
 __global__ __launch_bounds__(64) void rm_begin_kernel(RmArgs a) {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
@@ -56,13 +53,9 @@ __global__ __launch_bounds__(64) void rm_begin_kernel(RmArgs a) {
 __global__ __launch_bounds__(64) void rm_finish_kernel(RmArgs a) {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_streams) return;
-    const float p = a.records[s].out_sample_peak;
-    a.records[s].out_sample_peak_db = power_to_db(p * p, a.floor_db);
+    a.records[s].out_sample_peak_db = ps_peak_db(a.records[s].out_sample_peak, a.floor_db);
 }
 
-__device__ __forceinline__ uint32_t rm_to_aligned(const float* p) {  // floats up to the next 16-byte boundary
-    return ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2;
-}
 __device__ __forceinline__ uint32_t rm_uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 template <int CI, int FPT>
@@ -70,8 +63,6 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
     constexpr uint32_t kTile = kRmThreads * FPT;                   // frames of a tile
     extern __shared__ __attribute__((aligned(16))) float s_mem[];  // s_x [kTile][SI], s_y [kTile][SO] (+ shift)
     __shared__ uint32_t s_tm[kRmHeaderDwords + 2 * kRmMaxTerms];   // the matrix in use, as RmMatrix lays it out
-    __shared__ uint32_t s_over[kRmThreads / 64];
-    __shared__ float s_peak[kRmThreads / 64];
     constexpr uint32_t SI = rm_in_stride(CI);
     const uint32_t s = s_base + blockIdx.y, tid = threadIdx.x;
     const RmStreamCall call = a.calls[s];
@@ -86,7 +77,7 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
     // The tile's run of d_out, and where float j of it is staged.  Unpadded, the staging is shifted by up to three floats so that the
     // run's first aligned 16-byte vector is an aligned 16 bytes of LDS as well: the body then leaves LDS in ds_read_b128.
     float* dst = a.out + ((uint64_t)s * a.frames_capacity + first) * CO;
-    const uint32_t n_out = nf * CO, peel_out = min(n_out, rm_to_aligned(dst));
+    const uint32_t n_out = nf * CO, peel_out = min(n_out, ps_to_aligned(dst));
     const uint32_t y_shift = padded ? 0u : (4u - peel_out) & 3u;
     const auto y_at = [&](uint32_t j) { return padded ? (j >> co_shift) * SO + (j & (CO - 1)) : y_shift + j; };
 
@@ -99,7 +90,7 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
             const uint32_t fr = j / CI;
             s_x[fr * SI + (j - fr * CI)] = value;
         };
-        const uint32_t peel = min(n, rm_to_aligned(src));
+        const uint32_t peel = min(n, ps_to_aligned(src));
         const uint32_t nvec = (n - peel) >> 2, tail = (n - peel) & 3u;
         if (tid < peel) stage(tid, src[tid]);  // threads 0 .. 2 the head, threads 4 .. 6 the tail
         else if (tid >= 4 && tid < 4 + tail) stage(peel + 4 * nvec + (tid - 4), src[peel + 4 * nvec + (tid - 4)]);
@@ -124,8 +115,7 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
     __syncthreads();
 
     // ---- mix: frames tid, tid + 256, .. of the tile (a thread without a frame walks along on frame 0 and keeps nothing)
-    uint32_t over = 0;
-    float peak = 0.0f;
+    PsTally tally;
     uint32_t at_x[FPT], at_y[FPT];
     bool live[FPT];
 #pragma unroll
@@ -158,9 +148,7 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
 #pragma unroll
         for (uint32_t k = 0; k < FPT; ++k) {
             if (live[k]) {
-                const float m = fabsf(acc[k]);
-                over += m > 1.0f ? 1u : 0u;  // false for NaN, true for infinity
-                peak = fmaxf(peak, m);       // a NaN operand is ignored
+                tally.take(acc[k]);
                 s_y[at_y[k] + o] = acc[k];
             }
         }
@@ -181,26 +169,8 @@ __global__ __launch_bounds__(kRmThreads) void rm_main_kernel(RmArgs a, uint32_t 
         }
     }
 
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        over += (uint32_t)__shfl_xor((int)over, d);
-        peak = fmaxf(peak, __shfl_xor(peak, d));
-    }
-    if ((tid & 63u) == 0) {
-        s_over[tid >> 6] = over;
-        s_peak[tid >> 6] = peak;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (uint32_t w = 1; w < kRmThreads / 64; ++w) {
-            over += s_over[w];
-            peak = fmaxf(peak, s_peak[w]);
-        }
-        omx_program_remix_record* r = a.records + s;
-        if (over != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_over), (unsigned long long)over);
-        // bit patterns of non-negative floats order like the values; fmaxf never lets a NaN in
-        if (peak > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&r->out_sample_peak), __float_as_uint(peak));
-    }
+    tally.fold_workgroup<kRmThreads>();
+    if (tid == 0) tally.commit(a.records + s);
 }
 
 template <int CI, int FPT>
@@ -208,12 +178,9 @@ void rm_launch_tiles(const RmArgs& a, hipStream_t stream) {
     constexpr uint32_t kTile = kRmThreads * FPT;
     const uint64_t tiles = std::max<uint64_t>(((uint64_t)a.max_frames + kTile - 1) / kTile, 1);
     const size_t lds = ((size_t)kTile * (rm_in_stride(CI) + rm_out_stride(a.channels_out)) + 4) * sizeof(float);  // (+ 4: the output's shift)
-    // a launch holds at most 65535 streams in y and fewer than 2^32 threads: slabs of streams, as launch_pn_tiles
-    const uint64_t slab = std::max<uint64_t>(std::min<uint64_t>(65535, ((1ull << 24) - 1) / tiles), 1);
-    for (uint64_t base = 0; base < a.n_streams; base += slab) {
-        const dim3 grid((uint32_t)tiles, (uint32_t)std::min<uint64_t>(slab, a.n_streams - base));
-        hipLaunchKernelGGL((rm_main_kernel<CI, FPT>), grid, dim3(kRmThreads), lds, stream, a, (uint32_t)base);
-    }
+    for_stream_slabs(a.n_streams, tiles, [&](uint32_t base, uint32_t count) {
+        hipLaunchKernelGGL((rm_main_kernel<CI, FPT>), dim3((uint32_t)tiles, count), dim3(kRmThreads), lds, stream, a, base);
+    });
 }
 
 // the tile of the pair (rm_frames_per_thread): 8, 4 or 2 frames per thread with up to 2 input channels, 4 or 2 with up to 4, else 2

@@ -11,11 +11,6 @@ namespace omx {
 
 namespace {
 
-int rs_refuse(const char* who, const char* why) {
-    set_last_error(std::string("program loudness ") + who + ": " + why);
-    return OMX_ERR_INVALID;
-}
-
 double rs_i0(double v) {  // the power series, OMX_RESAMPLE_I0_TERMS terms behind the leading 1
     const double y = v * 0.5;
     double t = 1.0, s = 1.0;
@@ -30,12 +25,12 @@ double rs_i0(double v) {  // the power series, OMX_RESAMPLE_I0_TERMS terms behin
 
 int rs_plan(const omx_program_resample_rule* rule, omx_program_resample_info* info) {
     const char* who = "resample plan";
-    if (!rule || !info) return rs_refuse(who, "null rule or info");
-    if (rule->rate_in == 0 || rule->rate_out == 0 || rule->rate_in == rule->rate_out) return rs_refuse(who, "a rate of 0, or rate_in == rate_out");
-    if (rule->half_width < 8 || rule->half_width > 64 || (rule->half_width & 1u)) return rs_refuse(who, "half_width odd or outside 8 .. 64");
-    if (!std::isfinite(rule->beta) || rule->beta < 0.0f || rule->beta > 20.0f) return rs_refuse(who, "beta not finite or outside [0, 20]");
-    if (!(rule->cutoff > 0.5f && rule->cutoff <= 1.0f)) return rs_refuse(who, "cutoff not in (0.5, 1]");
-    if (rule->flags != 0) return rs_refuse(who, "a flag set");
+    if (!rule || !info) return pl_refuse(who, "null rule or info");
+    if (rule->rate_in == 0 || rule->rate_out == 0 || rule->rate_in == rule->rate_out) return pl_refuse(who, "a rate of 0, or rate_in == rate_out");
+    if (rule->half_width < 8 || rule->half_width > 64 || (rule->half_width & 1u)) return pl_refuse(who, "half_width odd or outside 8 .. 64");
+    if (!std::isfinite(rule->beta) || rule->beta < 0.0f || rule->beta > 20.0f) return pl_refuse(who, "beta not finite or outside [0, 20]");
+    if (!(rule->cutoff > 0.5f && rule->cutoff <= 1.0f)) return pl_refuse(who, "cutoff not in (0.5, 1]");
+    if (rule->flags != 0) return pl_refuse(who, "a flag set");
     const auto refuse_unsupported = [](const char* why) {
         set_last_error(std::string("unsupported configuration for the HIP path: resample plan: ") + why);
         return (int)OMX_ERR_UNSUPPORTED;
@@ -99,10 +94,10 @@ int ProgramLoudnessBank::resampler_configure(const omx_program_resample_rule* ru
     omx_program_resample_info info{};
     const int planned = rs_plan(rule, &info);
     if (planned != OMX_NONE) return planned;
-    if (channels == 0 || channels > OMX_MAX_CHANNELS) return rs_refuse(who, "channels outside 1 .. 8");
+    if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
     if (resampler_)
         for (const auto& m : resampler_->h_streams)
-            if (m.n != 0) return rs_refuse(who, "a stream of the resampler holds frames (reset every stream first)");
+            if (m.n != 0) return pl_refuse(who, "a stream of the resampler holds frames (reset every stream first)");
     if (resampler_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
     auto rs = resampler_ ? std::move(resampler_) : std::make_unique<ProgramResampler>();
     rs->rule = *rule;
@@ -145,7 +140,7 @@ RsArgs ProgramLoudnessBank::resampler_args() const {
 }
 
 int ProgramLoudnessBank::resampler_reset(const uint8_t* reset_mask) {
-    if (!resampler_) return rs_refuse("resampler_reset", "the resampler is not configured (omx_program_loudness_bank_resampler_configure)");
+    if (!resampler_) return pl_refuse("resampler_reset", "the resampler is not configured (omx_program_loudness_bank_resampler_configure)");
     ProgramResampler& rs = *resampler_;
     for (uint32_t s = 0; s < n_streams_; ++s) {
         RsStreamCall c{};
@@ -155,7 +150,7 @@ int ProgramLoudnessBank::resampler_reset(const uint8_t* reset_mask) {
         }
         rs.h_calls[s] = c;
     }
-    rs.staging.upload(rs.h_calls.data(), (size_t)n_streams_ * sizeof(RsStreamCall), rs.calls.ptr, last_stream_);
+    pl_upload_table(rs.staging, rs.h_calls, rs.calls.ptr, last_stream_);
     const RsArgs a = resampler_args();
     launch_rs_begin(a, false, last_stream_);
     launch_rs_finish(a, last_stream_);
@@ -167,21 +162,22 @@ int ProgramLoudnessBank::resampler_reset(const uint8_t* reset_mask) {
 int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
                                   const uint8_t* flush_mask, hipStream_t stream, const omx_program_resample_record** d_resampled) {
     const char* who = "resample";
-    if (!resampler_) return rs_refuse(who, "the resampler is not configured (omx_program_loudness_bank_resampler_configure)");
+    if (!resampler_) return pl_refuse(who, "the resampler is not configured (omx_program_loudness_bank_resampler_configure)");
     ProgramResampler& rs = *resampler_;
-    if (frames_capacity > 0xFFFFFFFFull || out_capacity > 0xFFFFFFFFull) return rs_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
+    if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
+        return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     RsArgs a = resampler_args();
     bool any_in = false, any_out = false;
     std::vector<RsStreamCall>& calls = rs.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const ProgramResampler::Mirror& m = rs.h_streams[s];
-        const uint64_t f = frames ? frames[s] : frames_capacity;
-        if (f > frames_capacity) return rs_refuse(who, "frames[s] > frames_capacity");
-        if (f != 0 && m.flushed) return rs_refuse(who, "frames for a flushed stream (reset it first)");
+        uint64_t f;
+        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
+        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
         const bool flush = m.flushed || (flush_mask && flush_mask[s]);
         const uint64_t n_new = m.n + f;
         const uint64_t e_new = rs_emitted(rs.info, n_new, m.e, flush);
-        if (e_new - m.e > out_capacity) return rs_refuse(who, "a stream would emit more than out_capacity frames");
+        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
         const unsigned __int128 pos = (unsigned __int128)m.e * a.M;
         RsStreamCall c{};
         c.n_old = m.n;
@@ -198,14 +194,12 @@ int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, c
         a.max_frames = std::max(a.max_frames, c.frames);
         a.max_emit = std::max(a.max_emit, c.emit);
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return rs_refuse(who, "null pcm");
+    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
     if (((uint64_t)a.max_emit + a.tile - 1) / a.tile * kRsThreads > 0xFFFFFFFFull) unsupported("programme resampler: call too long for one launch");
-    if (d_in && d_out) {  // out of place only: a tile would read what another has already written
-        const unsigned __int128 in_bytes = (unsigned __int128)n_streams_ * frames_capacity * a.channels * sizeof(float);
-        const unsigned __int128 out_bytes = (unsigned __int128)n_streams_ * out_capacity * a.channels * sizeof(float);
-        const unsigned __int128 lo_in = reinterpret_cast<uintptr_t>(d_in), lo_out = reinterpret_cast<uintptr_t>(d_out);
-        if (in_bytes != 0 && out_bytes != 0 && lo_in < lo_out + out_bytes && lo_out < lo_in + in_bytes) return rs_refuse(who, "d_in and d_out overlap");
-    }
+    // out of place only: a tile would read what another has already written
+    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
+    if (d_in && d_out && pl_ranges_overlap(d_in, frame_bytes * frames_capacity, d_out, frame_bytes * out_capacity))
+        return pl_refuse(who, "d_in and d_out overlap");
 
     for (uint32_t s = 0; s < n_streams_; ++s) {
         ProgramResampler::Mirror& m = rs.h_streams[s];
@@ -214,7 +208,7 @@ int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, c
         m.flushed = (calls[s].flags & kRsFlagFlush) != 0;
     }
     last_stream_ = stream;
-    rs.staging.upload(calls.data(), (size_t)n_streams_ * sizeof(RsStreamCall), rs.calls.ptr, stream);
+    pl_upload_table(rs.staging, calls, rs.calls.ptr, stream);
     a.in = d_in;
     a.out = d_out;
     a.frames_capacity = frames_capacity;
@@ -230,7 +224,7 @@ int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, c
 
 int ProgramLoudnessBank::fetch_resampled(uint64_t stream_index, omx_program_resample_record* dst) {
     if (!resampler_ || stream_index >= n_streams_)
-        return rs_refuse("fetch_resampled", "the resampler is not configured, or stream index out of range");
+        return pl_refuse("fetch_resampled", "the resampler is not configured, or stream index out of range");
     copy_out(dst, resampler_->records.ptr + stream_index, sizeof(*dst), false, last_stream_);
     return OMX_NONE;
 }

@@ -23,16 +23,13 @@
 //            not write keep the older frames, so a call of F < T - 1 frames, or of none, leaves the newest T - 1 frames in place.
 //   Only vector loads, vector stores and vector atomics are used.
 #include "program_resample.hpp"
+#include "program_stage_device.hpp"
 
 namespace omx {
 namespace {
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float power_to_db(float power, float floor) {  // level.rs:28-34, as program_peaks_kernels.hip
-    return power > 0.0f ? fmaxf(logf(power) * 4.3429448f, floor) : floor;
-}
 
 __device__ __forceinline__ float rs_x_at(const RsArgs& a, const RsStreamCall& call, uint32_t s, int64_t rel, uint32_t c) {
     if ((int64_t)call.n_old + rel < 0 || rel >= (int64_t)call.frames) return 0.0f;
@@ -72,8 +69,7 @@ __global__ __launch_bounds__(64) void rs_begin_kernel(RsArgs a, uint32_t whole_c
 __global__ __launch_bounds__(64) void rs_finish_kernel(RsArgs a) {
     const uint32_t s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_streams) return;
-    const float p = a.records[s].out_sample_peak;
-    a.records[s].out_sample_peak_db = power_to_db(p * p, a.floor_db);
+    a.records[s].out_sample_peak_db = ps_peak_db(a.records[s].out_sample_peak, a.floor_db);
 }
 
 // Where sample (frame fr, channel c) of the staging lies.  Up to 7 channels: interleaved, as in memory.  8 channels: two planes of four
@@ -110,8 +106,6 @@ template <int C>
 __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t s_base) {
     extern __shared__ __attribute__((aligned(16))) float s_x[];  // [span][C]; 8 channels: [2][span][4]
     __shared__ uint32_t s_head[3];                               // the tile's quotient (low, high) and remainder
-    __shared__ uint32_t s_over[kRsThreads / 64];
-    __shared__ float s_peak[kRsThreads / 64];
     const uint32_t s = s_base + blockIdx.y, tid = threadIdx.x;
     const RsStreamCall call = a.calls[s];
     const uint64_t first = (uint64_t)blockIdx.x * a.tile;  // the tile's first frame, counted from the call's first emitted frame
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
         // per thread before the first is used (one dependent load after the other, each waiting out its trip to memory, cost more than
         // the taps); the floats outside the aligned body as dwords.
         const float* src = a.in + ((uint64_t)s * a.frames_capacity + (uint64_t)rel_base) * C;
-        const uint32_t peel = min(n, ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u)) & 15u) >> 2);
+        const uint32_t peel = min(n, ps_to_aligned(src));
         const uint32_t nvec = (n - peel) >> 2, tail = (n - peel) & 3u;
         if (tid < peel) stage(tid, src[tid]);
         else if (tid >= 4 && tid < 4 + tail) stage(peel + 4 * nvec + (tid - 4), src[peel + 4 * nvec + (tid - 4)]);
@@ -168,8 +162,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
     }
     __syncthreads();
 
-    uint32_t over = 0;
-    float peak = 0.0f;
+    PsTally tally;
     if (tid < n_out) {
         const uint32_t v = r0 + tid * M, off = v / L, p = v - off * L;
         const float* h = a.table + p * 4;  // [T / 4][L][4]: taps k .. k + 3 of phase p
@@ -196,9 +189,7 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             y[c] = (acc[0][c] + acc[1][c]) + (acc[2][c] + acc[3][c]);
-            const float m = fabsf(y[c]);
-            over += m > 1.0f ? 1u : 0u;  // false for NaN, true for infinity
-            peak = fmaxf(peak, m);       // a NaN operand is ignored
+            tally.take(y[c]);
         }
         float* out = a.out + ((uint64_t)s * a.out_capacity + first + tid) * C;
         const uintptr_t base = reinterpret_cast<uintptr_t>(a.out);
@@ -213,26 +204,8 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
             for (int i = 0; i < C; ++i) out[i] = y[i];
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        over += (uint32_t)__shfl_xor((int)over, d);
-        peak = fmaxf(peak, __shfl_xor(peak, d));
-    }
-    if ((tid & 63u) == 0) {
-        s_over[tid >> 6] = over;
-        s_peak[tid >> 6] = peak;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        for (uint32_t w = 1; w < kRsThreads / 64; ++w) {
-            over += s_over[w];
-            peak = fmaxf(peak, s_peak[w]);
-        }
-        omx_program_resample_record* r = a.records + s;
-        if (over != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&r->samples_over), (unsigned long long)over);
-        // bit patterns of non-negative floats order like the values; fmaxf never lets a NaN in
-        if (peak > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&r->out_sample_peak), __float_as_uint(peak));
-    }
+    tally.fold_workgroup<kRsThreads>();
+    if (tid == 0) tally.commit(a.records + s);
 }
 
 // ---- carry: frame n of the stream at slot n mod (T - 1) of its ring

@@ -10,29 +10,20 @@ namespace omx {
 int ProgramLoudnessBank::timeline_rows(uint32_t stream_base, uint32_t n_streams, uint64_t first, uint64_t stride, uint64_t count,
                                        omx_program_timeline_row* d_rows, hipStream_t stream) {
     if (count == 0) return OMX_NONE;
-    if (!d_rows) {
-        set_last_error("program loudness timeline: null rows");
-        return OMX_ERR_INVALID;
-    }
-    if (stride == 0) {
-        set_last_error("program loudness timeline: stride 0");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "timeline";
+    if (!d_rows) return pl_refuse(who, "null rows");
+    if (stride == 0) return pl_refuse(who, "stride 0");
     // the last j in 64 bits, the launch grid and the row index in 32
-    if ((count - 1) > (~0ull - first) / stride || count > 0x7FFFFFFFull - kTlThreads || count * n_streams > 0xFFFFFFFFull) {
-        set_last_error("program loudness timeline: first + (count - 1) * stride or n_streams * count out of range");
-        return OMX_ERR_INVALID;
-    }
-    if (n_streams > kTlMaxStreams) {  // refused before anything is touched, not left to fail at the launch
-        set_last_error("program loudness timeline: more than 65535 streams in one call (use fetch_timeline per stream)");
-        return OMX_ERR_INVALID;
-    }
+    if ((count - 1) > (~0ull - first) / stride || count > 0x7FFFFFFFull - kTlThreads || count * n_streams > 0xFFFFFFFFull)
+        return pl_refuse(who, "first + (count - 1) * stride or n_streams * count out of range");
+    // refused before anything is touched, not left to fail at the launch
+    if (n_streams > kTlMaxStreams) return pl_refuse(who, "more than 65535 streams in one call (use fetch_timeline per stream)");
     const uint64_t last = first + (count - 1) * stride;
     uint64_t pitch = 1;  // 1 + the largest j that exists and is asked for
     for (uint32_t s = stream_base; s < stream_base + n_streams; ++s) pitch = std::max(pitch, std::min<uint64_t>(h_meta_[s].segments, last + 1));
     if (pitch > 0x7FFFFFFFull) unsupported("programme loudness timeline: more than 2^31 - 1 segments in a stream");
     last_stream_ = stream;
-    meta_staging_.upload(h_meta_.data(), (size_t)n_streams_ * sizeof(PlStreamMeta), meta_.ptr, stream);
+    pl_upload_table(meta_staging_, h_meta_, meta_.ptr, stream);
     // scratch: 20 bytes per block up to the last j asked for, grow-only, kept until the bank goes; every call redoes the scan from k = 0
     tl_gated_.reserve((size_t)n_streams * pitch);
     tl_threshold_.reserve((size_t)n_streams * pitch);
@@ -66,19 +57,11 @@ int ProgramLoudnessBank::timeline(uint64_t first, uint64_t stride, uint64_t coun
 
 int ProgramLoudnessBank::fetch_timeline(uint64_t stream_index, uint64_t first, uint64_t stride, uint64_t count, omx_program_timeline_row* dst) {
     if (bounded_) return bounded_refusal("fetch_timeline");
-    if (stream_index >= n_streams_) {
-        set_last_error("program loudness fetch_timeline: stream index out of range");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "fetch_timeline";
+    if (stream_index >= n_streams_) return pl_refuse(who, "stream index out of range");
     if (count == 0) return OMX_NONE;
-    if (!dst || stride == 0 || count > 0x7FFFFFFFull - kTlThreads) {
-        set_last_error("program loudness fetch_timeline: null rows, stride 0 or count out of range");
-        return OMX_ERR_INVALID;
-    }
-    if ((count - 1) > (~0ull - first) / stride) {
-        set_last_error("program loudness fetch_timeline: first + (count - 1) * stride out of range");
-        return OMX_ERR_INVALID;
-    }
+    if (!dst || stride == 0 || count > 0x7FFFFFFFull - kTlThreads) return pl_refuse(who, "null rows, stride 0 or count out of range");
+    if ((count - 1) > (~0ull - first) / stride) return pl_refuse(who, "first + (count - 1) * stride out of range");
     tl_rows_.reserve(count);
     const int rc = timeline_rows((uint32_t)stream_index, 1, first, stride, count, tl_rows_.ptr, last_stream_);
     if (rc < 0) return rc;
@@ -90,17 +73,13 @@ int ProgramLoudnessBank::measure_intervals(const omx_program_interval* intervals
                                            const omx_program_loudness_record** d_records) {
     if (bounded_) return bounded_refusal("measure_intervals");
     if (n == 0) return OMX_NONE;
-    if (!intervals || n > 0x7FFFFFFFull) {
-        set_last_error("program loudness measure_intervals: null intervals (or more than 2^31 - 1)");
-        return OMX_ERR_INVALID;
-    }
+    const char* who = "measure_intervals";
+    if (!intervals || n > 0x7FFFFFFFull) return pl_refuse(who, "null intervals (or more than 2^31 - 1)");
     for (uint64_t i = 0; i < n; ++i) {
         const omx_program_interval& in = intervals[i];
         if (in.stream >= n_streams_ || in.first_segment > h_meta_[in.stream].segments ||
-            in.segment_count > h_meta_[in.stream].segments - in.first_segment) {
-            set_last_error("program loudness measure_intervals: stream index out of range or interval outside the stored segments");
-            return OMX_ERR_INVALID;
-        }
+            in.segment_count > h_meta_[in.stream].segments - in.first_segment)
+            return pl_refuse(who, "stream index out of range or interval outside the stored segments");
     }
     h_interval_descs_.resize(n);
     for (uint64_t i = 0; i < n; ++i) {
@@ -110,7 +89,7 @@ int ProgramLoudnessBank::measure_intervals(const omx_program_interval* intervals
     last_stream_ = stream;
     interval_descs_.reserve(n);
     interval_records_.reserve(n);
-    interval_staging_.upload(h_interval_descs_.data(), (size_t)n * sizeof(PlIntervalDesc), interval_descs_.ptr, stream);
+    pl_upload_table(interval_staging_, h_interval_descs_, interval_descs_.ptr, stream);
     PlResultArgs r = result_args();
     r.records = interval_records_.ptr;
     launch_pl_intervals(r, interval_descs_.ptr, (uint32_t)n, stream);
@@ -122,10 +101,7 @@ int ProgramLoudnessBank::measure_intervals(const omx_program_interval* intervals
 int ProgramLoudnessBank::fetch_intervals(const omx_program_interval* intervals, uint64_t n, omx_program_loudness_record* dst) {
     if (bounded_) return bounded_refusal("fetch_intervals");
     if (n == 0) return OMX_NONE;
-    if (!dst) {
-        set_last_error("program loudness fetch_intervals: null records");
-        return OMX_ERR_INVALID;
-    }
+    if (!dst) return pl_refuse("fetch_intervals", "null records");
     const int rc = measure_intervals(intervals, n, last_stream_, nullptr);
     if (rc < 0) return rc;
     copy_out(dst, interval_records_.ptr, (size_t)n * sizeof(*dst), false, last_stream_);

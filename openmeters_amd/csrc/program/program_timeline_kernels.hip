@@ -13,25 +13,12 @@
 //          workgroup's largest j are not visited.  Then the lane forms its momentary and short-term block from e[] and stores its row.
 // Both orders depend on nothing but k and j: row j has the same bits through any (first, stride, count) and after later appends.
 // f64 sums, no fused multiply-add (-ffp-contract=off), no atomics.
-#include "program_loudness.hpp"
+#include "program_result_device.hpp"  // ms_to_lufs and the block expressions of the result pass
 
 namespace omx {
 namespace {
 
 constexpr uint32_t T = kTlThreads, E = kTlScanItems;
-
-__device__ __forceinline__ float ms_to_lufs(double ms, float floor) {  // as the result pass (loudness/processor.rs:57-66)
-    return ms > 0.0 ? (float)fmax(fma(log10(ms), 10.0, -0.691), (double)floor) : floor;
-}
-__device__ __forceinline__ double gating_block(const double* e, uint32_t j) {  // j >= 3
-    return (((e[j - 3] + e[j - 2]) + e[j - 1]) + e[j]) * 0.25;
-}
-__device__ __forceinline__ double short_term_block(const double* e, uint32_t j) {  // j >= 29
-    double acc = e[j - 29];
-#pragma unroll
-    for (uint32_t k = 1; k < 30; ++k) acc += e[j - 29 + k];
-    return acc / 30.0;
-}
 
 // blocks [0, limit) of a stream are needed: limit = min(segments, 1 + the last j asked for)
 __device__ __forceinline__ uint32_t stream_limit(const TlArgs& a, uint32_t s) {

@@ -10,7 +10,8 @@ def parse(path):
     for line in open(path):
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
-            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip().split("(")[0]
+            name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+            name = name.replace("(anonymous namespace)::", "").split("(")[0]  # (the kernels of an unnamed namespace keep their own names)
             out[name] = {}
         for key in ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]"):
             m = re.search(r"remark:\s+" + re.escape(key) + r": (\d+)", line)
