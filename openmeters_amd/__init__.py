@@ -38,6 +38,10 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_inspect.h)
     INSPECT_MAX_PAIRS, INSPECT_NAN, INSPECT_RECORD_DTYPE, INSPECT_SUMMARY_DTYPE, CProgramInspectChannel, CProgramInspectInfo,
     CProgramInspectPair, CProgramInspectRecord, CProgramInspectRule, CProgramInspectSummary, InspectRule, inspect_plan,
     inspect_rule_default, inspect_summarize)
+from .program_loudness import (  # noqa: F401  (include/omx/program_edit.h)
+    EDIT_CLIP_DTYPE, EDIT_CURVE_EQUAL_POWER, EDIT_CURVE_LINEAR, EDIT_CURVE_POINTS, EDIT_CURVE_RAISED_COSINE, EDIT_INFO_DTYPE, EDIT_MAX_FADE,
+    EDIT_MAX_OUTPUTS, EDIT_MAX_POSITION, EDIT_RECORD_DTYPE, CProgramEditClip, CProgramEditInfo, CProgramEditRecord, CProgramTrimRule,
+    EditClip, TrimRule, edit_curve, edit_extent, edit_gain, edit_plan, edit_table, edit_trim)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -15,6 +15,7 @@
 #include "program_resample.hpp"
 #include "program_remix.hpp"
 #include "program_inspect.hpp"
+#include "program_edit.hpp"
 
 namespace omx {
 
@@ -154,6 +155,12 @@ public:
     int inspect(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, hipStream_t stream,
                 const omx_program_inspect_record** d_inspected);
     int fetch_inspected(uint64_t stream_index, omx_program_inspect_record* dst);
+    // include/omx/program_edit.h (program_edit.cpp)
+    int edit_configure(uint32_t channels, uint32_t max_outputs);
+    int edit(const float* d_in, uint64_t frames_capacity, const uint32_t* frames_in, const omx_program_edit_clip* clips, uint64_t n_clips,
+             float* d_out, uint64_t out_capacity, uint32_t n_out, const uint64_t* out_first, const uint32_t* out_frames, hipStream_t stream,
+             const omx_program_edit_record** d_edited);
+    int fetch_edited(uint64_t output_index, omx_program_edit_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -238,6 +245,8 @@ private:
     // signal QC: nothing is allocated or launched until inspect_configure
     InArgs inspect_args() const;
     std::unique_ptr<ProgramInspector> inspector_;
+    // edit: nothing is allocated or launched until edit_configure
+    std::unique_ptr<ProgramEdit> edit_;
 };
 
 }  // namespace omx

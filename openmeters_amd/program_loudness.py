@@ -513,6 +513,142 @@ def inspect_summarize(api: Api, rule: InspectRule, record: np.ndarray) -> np.nda
     return out[0]
 
 
+class CProgramEditClip(C.Structure):
+    """omx_program_edit_clip (include/omx/program_edit.h)"""
+    _fields_ = [("src_stream", C.c_uint32), ("dst_stream", C.c_uint32), ("src_first", C.c_uint64), ("dst_first", C.c_uint64),
+                ("frames", C.c_uint64), ("fade_in_frames", C.c_uint32), ("fade_out_frames", C.c_uint32), ("fade_in_curve", C.c_uint8),
+                ("fade_out_curve", C.c_uint8), ("flags", C.c_uint16), ("gain", C.c_float)]
+
+
+class CProgramEditInfo(C.Structure):
+    """omx_program_edit_info (include/omx/program_edit.h)"""
+    _fields_ = [("tile_frames", C.c_uint32), ("channels", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class CProgramTrimRule(C.Structure):
+    """omx_program_trim_rule (include/omx/program_edit.h)"""
+    _fields_ = [("keep_head", C.c_uint64), ("keep_tail", C.c_uint64), ("pad_head", C.c_uint64), ("pad_tail", C.c_uint64),
+                ("fade_in_frames", C.c_uint32), ("fade_out_frames", C.c_uint32), ("fade_in_curve", C.c_uint8), ("fade_out_curve", C.c_uint8),
+                ("flags", C.c_uint16), ("_pad", C.c_uint32)]
+
+
+class CProgramEditRecord(C.Structure):
+    """omx_program_edit_record (include/omx/program_edit.h)"""
+    _fields_ = [("out_first", C.c_uint64), ("frames", C.c_uint64), ("silent_frames", C.c_uint64), ("faded_frames", C.c_uint64),
+                ("mixed_frames", C.c_uint64), ("samples_over", C.c_uint64), ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float),
+                ("clips", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+EDIT_CLIP_DTYPE = np.dtype([("src_stream", "<u4"), ("dst_stream", "<u4"), ("src_first", "<u8"), ("dst_first", "<u8"), ("frames", "<u8"),
+                            ("fade_in_frames", "<u4"), ("fade_out_frames", "<u4"), ("fade_in_curve", "u1"), ("fade_out_curve", "u1"),
+                            ("flags", "<u2"), ("gain", "<f4")])
+EDIT_INFO_DTYPE = np.dtype([("tile_frames", "<u4"), ("channels", "<u4"), ("_pad", "<u4", (2,))])
+EDIT_RECORD_DTYPE = np.dtype([("out_first", "<u8"), ("frames", "<u8"), ("silent_frames", "<u8"), ("faded_frames", "<u8"),
+                              ("mixed_frames", "<u8"), ("samples_over", "<u8"), ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"),
+                              ("clips", "<u4"), ("_pad", "<u4")])
+assert C.sizeof(CProgramEditClip) == 48 and C.sizeof(CProgramEditInfo) == 16 and C.sizeof(CProgramTrimRule) == 48
+assert C.sizeof(CProgramEditRecord) == 64
+assert EDIT_CLIP_DTYPE.itemsize == 48 and EDIT_INFO_DTYPE.itemsize == 16 and EDIT_RECORD_DTYPE.itemsize == 64
+EDIT_CURVE_LINEAR, EDIT_CURVE_EQUAL_POWER, EDIT_CURVE_RAISED_COSINE = 0, 1, 2   # omx_program_edit_clip.fade_*_curve
+EDIT_CURVE_POINTS = 4097
+EDIT_MAX_FADE = 1 << 24
+EDIT_MAX_OUTPUTS = 1 << 24
+EDIT_MAX_POSITION = 1 << 40
+
+
+@dataclass
+class EditClip:
+    """omx_program_edit_clip: source frames [src_first, src_first + frames) of input stream src_stream land at output frames
+    [dst_first, dst_first + frames) of output stream dst_stream, times gain, under a fade-in and a fade-out (EDIT_CURVE_*)"""
+    src_stream: int = 0
+    dst_stream: int = 0
+    src_first: int = 0
+    dst_first: int = 0
+    frames: int = 0
+    fade_in_frames: int = 0
+    fade_out_frames: int = 0
+    fade_in_curve: int = EDIT_CURVE_LINEAR
+    fade_out_curve: int = EDIT_CURVE_LINEAR
+    flags: int = 0
+    gain: float = 1.0
+
+    def to_row(self) -> tuple:
+        return (self.src_stream, self.dst_stream, self.src_first, self.dst_first, self.frames, self.fade_in_frames, self.fade_out_frames,
+                self.fade_in_curve, self.fade_out_curve, self.flags, self.gain)
+
+
+def edit_table(clips) -> np.ndarray:
+    """A clip table as a contiguous EDIT_CLIP_DTYPE array, from a sequence of EditClip or from such an array"""
+    if isinstance(clips, np.ndarray):
+        return np.ascontiguousarray(clips, EDIT_CLIP_DTYPE).reshape(-1)
+    return np.array([c.to_row() for c in clips], EDIT_CLIP_DTYPE).reshape(-1)
+
+
+@dataclass
+class TrimRule:
+    """omx_program_trim_rule: frames of the found silence to keep in front and behind, frames of exact zero to put in front and
+    behind, and the fades of the cut (clamped to the kept length)"""
+    keep_head: int = 0
+    keep_tail: int = 0
+    pad_head: int = 0
+    pad_tail: int = 0
+    fade_in_frames: int = 0
+    fade_out_frames: int = 0
+    fade_in_curve: int = EDIT_CURVE_LINEAR
+    fade_out_curve: int = EDIT_CURVE_LINEAR
+    flags: int = 0
+
+    def to_c(self) -> CProgramTrimRule:
+        return CProgramTrimRule(self.keep_head, self.keep_tail, self.pad_head, self.pad_tail, self.fade_in_frames, self.fade_out_frames,
+                                self.fade_in_curve, self.fade_out_curve, self.flags, 0)
+
+
+def edit_plan(api: Api, channels: int) -> np.ndarray:
+    """The plan of a channel count (omx_program_edit_plan) as an EDIT_INFO_DTYPE scalar: the main kernel's tile in output frames.
+    Needs no device."""
+    out = np.zeros((1,), EDIT_INFO_DTYPE)
+    api.check(api.fn("program_edit_plan", C.c_int, [C.c_uint32, C.c_void_p])(channels, out.ctypes.data))
+    return out[0]
+
+
+def edit_curve(api: Api, curve: int) -> np.ndarray:
+    """The table of a fade curve (omx_program_edit_curve): f32 [4097].  Needs no device."""
+    out = np.zeros((EDIT_CURVE_POINTS,), np.float32)
+    api.check(api.fn("program_edit_curve", C.c_int, [C.c_uint32, C.c_void_p])(curve, out.ctypes.data))
+    return out
+
+
+def edit_gain(api: Api, curve: int, fade_frames: int, index: int) -> np.float32:
+    """The fade factor at `index` of a fade of `fade_frames` frames (omx_program_edit_gain), by the function the kernel runs.  Needs
+    no device."""
+    out = C.c_float()
+    api.check(api.fn("program_edit_gain", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p])(curve, fade_frames, index, C.byref(out)))
+    return np.float32(out.value)
+
+
+def edit_extent(api: Api, clips, frames_in: Sequence[int], n_out: int) -> np.ndarray:
+    """Validate a clip table against the frames of the input streams (omx_program_edit_extent) -> uint64 [n_out]: one past the last
+    covered frame of every output stream.  Needs no device."""
+    table = edit_table(clips)
+    fr = np.ascontiguousarray(frames_in, np.uint32).reshape(-1)
+    out = np.zeros((n_out,), np.uint64)
+    api.check(api.fn("program_edit_extent", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])(
+        table.ctypes.data if table.size else None, table.size, fr.size, fr.ctypes.data if fr.size else None, n_out,
+        out.ctypes.data if n_out else None))
+    return out
+
+
+def edit_trim(api: Api, record: np.ndarray, rule: TrimRule, src_stream: int = 0, dst_stream: int = 0):
+    """The clip that cuts a stream where inspect found silence (omx_program_edit_trim), from one INSPECT_RECORD_DTYPE record ->
+    (EditClip, the frames of the output: pad_head + the clip + pad_tail).  Needs no device."""
+    rec = np.ascontiguousarray(np.asarray(record, INSPECT_RECORD_DTYPE).reshape(1))
+    c, clip, total = rule.to_c(), np.zeros((1,), EDIT_CLIP_DTYPE), C.c_uint64()
+    api.check(api.fn("program_edit_trim", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])(
+        rec.ctypes.data, C.byref(c), src_stream, dst_stream, clip.ctypes.data, C.byref(total)))
+    row = clip[0]
+    return EditClip(*[int(row[f]) for f in EDIT_CLIP_DTYPE.names[:-1]], float(row["gain"])), int(total.value)
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -1000,4 +1136,41 @@ class ProgramLoudnessBank:
         out = np.zeros((1,), INSPECT_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_inspected", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_edit.h
+    def configure_edit(self, channels: int, max_outputs: int):
+        """Set the channel count of the PCM the edit pass takes and the largest number of output streams of a call; allocates the
+        records and uploads the curve tables.  Allowed at any time; edit calls still enqueued are waited for."""
+        self.api.check(self.api.fn("program_loudness_bank_edit_configure", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32])(
+            self._h, channels, max_outputs))
+
+    def edit(self, d_in: int, frames_capacity: int, clips, d_out: int, out_capacity: int, out_frames: Sequence[int],
+             out_first: Optional[Sequence[int]] = None, frames_in: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Render the clip table (a sequence of EditClip or an EDIT_CLIP_DTYPE array, sorted by (dst_stream, dst_first)) from d_in (f32
+        [n_streams][frames_capacity][channels]; frames_in[s]: the frames stream s holds, None: the whole row) into d_out (f32
+        [len(out_frames)][out_capacity][channels]) on `stream`: output frames [out_first[o], out_first[o] + out_frames[o]) of output
+        stream o land at d_out[o][0 ..]; out_first None: 0.  Out of place; no float beyond a window is written.  Returns the device
+        pointer to omx_program_edit_record[max_outputs] (EDIT_RECORD_DTYPE), entries below len(out_frames) written fresh by every call."""
+        table = edit_table(clips)
+        fr = self._per_stream(frames_in, np.uint32, "frames_in")
+        of = np.ascontiguousarray(out_frames, np.uint32).reshape(-1)
+        first = None if out_first is None else np.ascontiguousarray(out_first, np.uint64).reshape(-1)
+        if first is not None and first.size != of.size:
+            raise ValueError(f"out_first: {first.size} entries for {of.size} outputs")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_edit", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                         table.ctypes.data if table.size else None, table.size, C.c_void_p(d_out or 0), out_capacity, of.size,
+                         first.ctypes.data if first is not None else None, of.ctypes.data if of.size else None, C.c_void_p(stream or 0),
+                         C.byref(out)))
+        return out.value or 0
+
+    def fetch_edited(self, output_index: int) -> np.ndarray:
+        """One output's record of the last edit call as an EDIT_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), EDIT_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_edited", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, output_index, out.ctypes.data))
         return out[0]
