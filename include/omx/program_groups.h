@@ -35,7 +35,7 @@
  *     segments = sum of n_m;  frames = segments * the segment length in frames;  gating_blocks = |G|;  short_term_blocks = |ST|
  *     momentary_* / short_term_* (the latest blocks) = those of the LAST member: its last block, 0 / the floor when it has fewer than
  *       4 / 30 segments or the group is empty
- *     max_true_peak_db = the floor, as for an interval;  overflow = 0
+ *     max_true_peak_db = the floor, as for an interval (program_peak_timeline.h measures the peaks of a group);  overflow = 0
  *   An empty group, or one with no passing block, has integrated = the floor and range = 0.
  *   SUMMATION ORDER.  Block i of G (and of ST), counted from 0 over the concatenation, goes to lane i mod 256; each lane adds its
  *   blocks in ascending i; then the binary tree of the result pass runs.  So a group of ONE member has the bytes of

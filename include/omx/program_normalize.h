@@ -82,6 +82,7 @@ int omx_program_loudness_bank_plan_gains(omx_program_loudness_bank* b, const omx
  * earlier measure_groups returned, as any bank call may.  Source loudness: the group record's.  Source peak: the maximum of
  * max_true_peak_db over the STREAMS of the group's members, whole-programme figures: the peak records have no time axis, so for a
  * member that is a part of a stream this is conservative (the gain may be lower than the part alone would need, never higher).
+ * omx_program_loudness_bank_plan_part_gains (program_peak_timeline.h) takes the peak of the members' own segments instead.
  * A stream counts once however often it appears.  An empty group: OMX_GAIN_BY_NO_MEASUREMENT, source_peak_db = the floor.
  * *d_gains: device array [n_groups], same buffer and lifetime as above.  n_groups == 0 (with a good rule): OMX_NONE, nothing is
  * planned and an earlier plan stays. */

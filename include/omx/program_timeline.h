@@ -29,6 +29,7 @@
  *   pass's own definitions (and its own code), as if that were the whole programme.
  *     segments = segment_count;  frames = segment_count * the segment length in frames;  overflow = 0
  *     max_true_peak_db = the floor: the peak records have no time axis, so a part of a programme has no peak of its own here
+ *       (program_peak_timeline.h measures the peaks of an interval).
  *   A count of 0, or fewer than 4 / 30 segments, gives the empty fields a young stream has.  The interval [0, segments[s]) has the
  *   bits of omx_program_loudness_bank_fetch(s) in every field but frames, overflow and max_true_peak_db. */
 #ifndef OMX_PROGRAM_TIMELINE_H

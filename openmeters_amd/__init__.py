@@ -42,6 +42,8 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_edit.h)
     EDIT_CLIP_DTYPE, EDIT_CURVE_EQUAL_POWER, EDIT_CURVE_LINEAR, EDIT_CURVE_POINTS, EDIT_CURVE_RAISED_COSINE, EDIT_INFO_DTYPE, EDIT_MAX_FADE,
     EDIT_MAX_OUTPUTS, EDIT_MAX_POSITION, EDIT_RECORD_DTYPE, CProgramEditClip, CProgramEditInfo, CProgramEditRecord, CProgramTrimRule,
     EditClip, TrimRule, edit_curve, edit_extent, edit_gain, edit_plan, edit_table, edit_trim)
+from .program_loudness import (  # noqa: F401  (include/omx/program_peak_timeline.h)
+    PART_PEAK_DTYPE, PEAK_ROW_DTYPE, CProgramPartPeak, CProgramPeakRow)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

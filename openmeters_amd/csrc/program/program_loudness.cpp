@@ -120,6 +120,7 @@ int ProgramLoudnessBank::reset(const uint8_t* reset_mask) {
 int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, const uint32_t* frames, const uint8_t* reset_mask,
                                  uint32_t channels_in, float sample_rate, const uint8_t positions[OMX_MAX_CHANNELS], hipStream_t stream) {
     const char* who = "process";
+    const uint32_t seg_before = seg_, channels_before = channels_;  // the layout the peak timeline's stored keys were written with
     if (!pl_capacity_ok(frames_capacity)) return pl_refuse(who, "frames_capacity beyond 2^32 - 1");
     // (a clamped count with the caller's stride would read the wrong samples)
     if (!pl_channels_ok(channels_in)) return pl_refuse(who, "channels outside 1 .. 8");
@@ -153,6 +154,11 @@ int ProgramLoudnessBank::process(const float* d_pcm, uint64_t frames_capacity, c
         PlStreamMeta& m = h_meta_[s];
         PlStreamCall& c = h_calls_[s];
         c.reset = (reset_mask && reset_mask[s]) ? 1u : 0u;
+        if (c.reset && peak_timeline_on_ && m.frames != 0) {  // the peak segments the stream has stored go back to zero (measure_peaks)
+            const uint64_t row = (uint64_t)channels_before * kPtKinds;
+            const uint64_t at = (uint64_t)s * (capacity_ + 1) * row, n = std::min<uint64_t>((m.frames + seg_before - 1) / seg_before, capacity_ + 1) * row;
+            for (uint64_t e = 0; e < n; e += kPtClearChunk) h_pt_clear_.push_back(PtClearItem{at + e, (uint32_t)std::min<uint64_t>(kPtClearChunk, n - e), 0u});
+        }
         if (c.reset) m = PlStreamMeta{0, 0, 0};
         const uint64_t room = bounded_ ? ~0ull : capacity_ * seg_ - m.frames;  // a full stream takes no more samples; a bounded one never fills
         const uint64_t want = any ? (frames ? frames[s] : frames_capacity) : 0;

@@ -16,6 +16,7 @@
 #include "program_remix.hpp"
 #include "program_inspect.hpp"
 #include "program_edit.hpp"
+#include "program_peak_timeline.hpp"
 
 namespace omx {
 
@@ -161,6 +162,18 @@ public:
              float* d_out, uint64_t out_capacity, uint32_t n_out, const uint64_t* out_first, const uint32_t* out_frames, hipStream_t stream,
              const omx_program_edit_record** d_edited);
     int fetch_edited(uint64_t output_index, omx_program_edit_record* dst);
+    // include/omx/program_peak_timeline.h (program_peak_timeline.cpp)
+    int set_peak_timeline(bool on);
+    int peak_rows(uint64_t first, uint64_t stride, uint64_t count, omx_program_peak_row* d_rows, hipStream_t stream);
+    int fetch_peak_rows(uint64_t stream_index, uint64_t first, uint64_t stride, uint64_t count, omx_program_peak_row* dst);
+    int measure_interval_peaks(const omx_program_interval* intervals, uint64_t n, hipStream_t stream, const omx_program_part_peak** d_peaks);
+    int fetch_interval_peaks(const omx_program_interval* intervals, uint64_t n, omx_program_part_peak* dst);
+    int measure_group_peaks(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
+                            hipStream_t stream, const omx_program_part_peak** d_peaks);
+    int fetch_group_peaks(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
+                          omx_program_part_peak* dst);
+    int plan_part_gains(const omx_program_gain_rule* rule, const omx_program_interval* members, uint64_t n_members,
+                        const omx_program_group* groups, uint64_t n_groups, hipStream_t stream, const omx_program_gain_record** d_gains);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -201,6 +214,25 @@ private:
     DeviceBuffer<omx_program_peak_record> peak_records_;
     DeviceBuffer<float> peak_delay_;
     DeviceBuffer<PkPartial> peak_partials_;
+    // peak timeline: nothing is allocated or launched while it is off
+    void peak_timeline_off();
+    unsigned long long* peak_timeline_keys(bool frames_taken, hipStream_t stream);
+    int peak_rows_refusal(uint32_t n_streams, uint64_t first, uint64_t stride, uint64_t count, const void* rows) const;
+    void peak_rows_of(uint32_t stream_base, uint32_t n_streams, uint64_t first, uint64_t stride, uint64_t count, omx_program_peak_row* d_rows,
+                      hipStream_t stream);
+    int part_peaks(const omx_program_interval* members, uint64_t n_members, const omx_program_group* groups, uint64_t n_groups,
+                   hipStream_t stream, const omx_program_part_peak** d_peaks, bool for_gains);
+    bool peak_timeline_on_ = false;
+    DeviceBuffer<unsigned long long> pt_keys_;  // [n_streams][capacity_ + 1][channels_][2], reserved by the first call that brings frames
+    std::vector<PtClearItem> h_pt_clear_;       // the current call: the stored keys of the streams it resets, in runs of at most
+    DeviceBuffer<PtClearItem> pt_clear_;        // kPtClearChunk, in the layout of before the call (its rate and channel count)
+    BlobStaging pt_clear_staging_;
+    DeviceBuffer<omx_program_peak_row> pt_rows_;  // fetch_peak_rows' device rows
+    DeviceBuffer<uint8_t> pt_tables_;             // [PtMember x n_members][PtPart x n_parts] of the current call
+    DeviceBuffer<omx_program_part_peak> pt_records_;
+    std::vector<uint8_t> h_pt_tables_;
+    std::vector<uint64_t> h_pt_before_;           // part_peaks' running sums over the member table
+    BlobStaging pt_staging_;
     // timeline and intervals: nothing is allocated or launched until one of their functions is called
     DeviceBuffer<double> tl_gated_, tl_threshold_;
     DeviceBuffer<uint32_t> tl_above_;

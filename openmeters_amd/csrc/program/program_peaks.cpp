@@ -14,6 +14,7 @@ int ProgramLoudnessBank::set_peaks(bool on) {
         OMX_HIP(hipGetLastError());
         OMX_HIP(hipStreamSynchronize(last_stream_));  // (the first process call may come on another stream)
     } else {
+        peak_timeline_off();  // (the peak timeline lives on the peak pass: off with it)
         OMX_HIP(hipStreamSynchronize(last_stream_));  // (a result pass that reads the records may still be in flight)
         peak_records_.release();
         peak_delay_.release();
@@ -39,6 +40,11 @@ void ProgramLoudnessBank::measure_peaks(const float* d_pcm, uint64_t frames_capa
     p.delay = peak_delay_.ptr;
     p.records = peak_records_.ptr;
     pl_true_peak_fir(p.fir4, p.fir2);
+    if (peak_timeline_on_) {  // (in front of the tile pass: the keys of a reset stream are cleared before the call's frames merge in)
+        p.tl_keys = peak_timeline_keys(p.n_tiles != 0, stream);
+        p.tl_rows = capacity_ + 1;
+        p.seg = seg_;
+    }
     if (p.n_tiles != 0) {
         peak_partials_.reserve((size_t)n_streams_ * channels_ * p.n_tiles);
         p.partials = peak_partials_.ptr;

@@ -33,6 +33,10 @@ struct PkArgs {
     omx_program_peak_record* records;  // [n_streams]: the running records (the fold reads and rewrites them)
     float fir4[12][3];          // TRUE_PEAK_FIRS.0 (loudness/processor.rs:90-97)
     float fir2[24];             // TRUE_PEAK_FIRS.1
+    // the peak timeline (program_peak_timeline.hpp), read by the timeline form of the tile kernel alone; null: the timeline is off
+    unsigned long long* tl_keys;  // [n_streams][tl_rows][channels][2]
+    uint64_t tl_rows;             // rows per stream: capacity in segments + 1
+    uint32_t seg;                 // frames per segment
 };
 void launch_pk_tiles(const PkArgs& a, hipStream_t stream);
 void launch_pk_fold(const PkArgs& a, hipStream_t stream);

@@ -18,6 +18,12 @@
 //   reduce  : (value, first frame) as one 64-bit key, value bits above the complemented frame: the larger value wins, the earlier
 //             frame wins among equals (values are >= +0 and never NaN, so their bit patterns order like the values).  Six shuffle
 //             steps per wavefront, then one 16-byte store per (stream, channel, tile).  No atomics.
+//   timeline: the second instantiation, run only by a bank with the peak timeline on (include/omx/program_peak_timeline.h).  A lane
+//             also keeps the sixteen v of its run; where a segment boundary cuts a run of the wavefront (a few lanes per tile), the
+//             maxima of the two sides are formed from them without running the interpolator again.  The wavefront reduces one key
+//             pair per segment the tile touches (at most five), the tile's partial is their maximum, and lanes 0 / 1 merge each into
+//             the stream's keys with ONE global 64-bit atomic maximum per (segment, channel, kind): a maximum is order-free, so the
+//             atomics cost no determinism, and a call boundary inside a segment merges by itself.
 // Fold, one workgroup per stream, one wavefront per channel slot: the partials in tile order into the running record, the frame base
 // added, the delay line of the next call written, the record's dB fields and maxima rebuilt.
 #include "program_loudness.hpp"
@@ -47,72 +53,110 @@ __device__ __forceinline__ unsigned long long wave_max(unsigned long long k) {
     return k;
 }
 
-// the peaks of the first n_here (<= 16) samples of a run.  w[H + n] = sample n of the run, w[0 .. H) = the H samples before it.
-// k_* = index in the run of the first sample that reaches the maximum (0 when the maximum is 0).
+// |x| and v of the frames m (.._lo) and m + R / 2 (.._hi) of a run.  w[H + n] = sample n of the run, w[0 .. H) = the H samples before
+// it; pair[j] = {w[j], w[j + R / 2]}: the same window position of the older and of the newer half of the run.
 template <int DL>
-__device__ __forceinline__ void run_peaks(const float (&w)[R + (DL > 1 ? DL - 1 : 0)], uint32_t n_here, const float (&fir)[DL == 12 ? 36 : 24], float& tp,
-                                          uint32_t& k_tp, float& sp, uint32_t& k_sp) {
+__device__ __forceinline__ void run_values(const float (&w)[R + (DL > 1 ? DL - 1 : 0)], const v2f (&pair)[R / 2 + (DL > 1 ? DL - 1 : 0) + 1],
+                                           const float (&fir)[DL == 12 ? 36 : 24], int m, float& x_lo, float& x_hi, float& v_lo, float& v_hi) {
     constexpr int H = DL > 1 ? DL - 1 : 0, HALF = R / 2;
-    v2f pair[HALF + H + 1];  // pair[j] = {w[j], w[j + HALF]}: the same window position of the older and of the newer half of the run
+    x_lo = fabsf(w[H + m]);
+    x_hi = fabsf(w[H + m + HALF]);
+    v_lo = x_lo;
+    v_hi = x_hi;
+    if constexpr (DL == 12) {
+        // (three phases of one window position = three independent chains side by side)
+        v2f o0 = pair[H + m] * v2f{fir[0], fir[0]};
+        v2f o1 = pair[H + m] * v2f{fir[1], fir[1]};
+        v2f o2 = pair[H + m] * v2f{fir[2], fir[2]};
+#pragma unroll
+        for (int i = 1; i < 12; ++i) {
+            const v2f p0 = pair[H + m - i] * v2f{fir[3 * i], fir[3 * i]};
+            const v2f p1 = pair[H + m - i] * v2f{fir[3 * i + 1], fir[3 * i + 1]};
+            const v2f p2 = pair[H + m - i] * v2f{fir[3 * i + 2], fir[3 * i + 2]};
+            o0 = o0 + p0;
+            o1 = o1 + p1;
+            o2 = o2 + p2;
+        }
+        v_lo = fmaxf(fmaxf(fmaxf(v_lo, fabsf(o0.x)), fabsf(o1.x)), fabsf(o2.x));
+        v_hi = fmaxf(fmaxf(fmaxf(v_hi, fabsf(o0.y)), fabsf(o1.y)), fabsf(o2.y));
+    } else if constexpr (DL == 24) {
+        v2f o = pair[H + m] * v2f{fir[0], fir[0]};
+#pragma unroll
+        for (int i = 1; i < 24; ++i) o = o + pair[H + m - i] * v2f{fir[i], fir[i]};
+        v_lo = fmaxf(v_lo, fabsf(o.x));
+        v_hi = fmaxf(v_hi, fabsf(o.y));
+    }
+}
+
+// a running maximum with the index of the first sample that reaches it (0 while the maximum is 0), and its merge with a LATER one
+struct PkFirstMax {
+    float v = 0.0f;
+    uint32_t k = 0;
+    // strictly greater, in time order: the first frame of the maximum.  A NaN (every operand of the max was one) compares false.
+    __device__ __forceinline__ void take(bool in, float x, uint32_t at) {
+        if (in && x > v) {
+            v = x;
+            k = at;
+        }
+    }
+    __device__ __forceinline__ PkFirstMax then(const PkFirstMax& later) const { return later.v > v ? later : *this; }  // the older wins among equals
+};
+
+// the peaks of the first n_here (<= 16) samples of a run.
+// k_* = index in the run of the first sample that reaches the maximum (0 when the maximum is 0).
+// KEEP (the timeline form): v_all[n] = v of sample n of the run, for run_sides.
+template <int DL, bool KEEP = false>
+__device__ __forceinline__ void run_peaks(const float (&w)[R + (DL > 1 ? DL - 1 : 0)], uint32_t n_here, const float (&fir)[DL == 12 ? 36 : 24], float& tp,
+                                          uint32_t& k_tp, float& sp, uint32_t& k_sp, float* v_all = nullptr) {
+    constexpr int H = DL > 1 ? DL - 1 : 0, HALF = R / 2;
+    v2f pair[HALF + H + 1];
 #pragma unroll
     for (int j = 0; j < HALF + H; ++j) pair[j] = v2f{w[j], w[j + HALF]};
-    float t_lo = 0.0f, t_hi = 0.0f, s_lo = 0.0f, s_hi = 0.0f;
-    uint32_t kt_lo = 0, kt_hi = 0, ks_lo = 0, ks_hi = 0;
+    PkFirstMax t_lo, t_hi, s_lo, s_hi;
 #pragma unroll
     for (int m = 0; m < HALF; ++m) {
         const bool in_lo = (uint32_t)m < n_here, in_hi = (uint32_t)(m + HALF) < n_here;
-        const float x_lo = fabsf(w[H + m]), x_hi = fabsf(w[H + m + HALF]);
-        float v_lo = x_lo, v_hi = x_hi;
-        if constexpr (DL == 12) {
-            // (three phases of one window position = three independent chains side by side)
-            v2f o0 = pair[H + m] * v2f{fir[0], fir[0]};
-            v2f o1 = pair[H + m] * v2f{fir[1], fir[1]};
-            v2f o2 = pair[H + m] * v2f{fir[2], fir[2]};
-#pragma unroll
-            for (int i = 1; i < 12; ++i) {
-                const v2f p0 = pair[H + m - i] * v2f{fir[3 * i], fir[3 * i]};
-                const v2f p1 = pair[H + m - i] * v2f{fir[3 * i + 1], fir[3 * i + 1]};
-                const v2f p2 = pair[H + m - i] * v2f{fir[3 * i + 2], fir[3 * i + 2]};
-                o0 = o0 + p0;
-                o1 = o1 + p1;
-                o2 = o2 + p2;
-            }
-            v_lo = fmaxf(fmaxf(fmaxf(v_lo, fabsf(o0.x)), fabsf(o1.x)), fabsf(o2.x));
-            v_hi = fmaxf(fmaxf(fmaxf(v_hi, fabsf(o0.y)), fabsf(o1.y)), fabsf(o2.y));
-        } else if constexpr (DL == 24) {
-            v2f o = pair[H + m] * v2f{fir[0], fir[0]};
-#pragma unroll
-            for (int i = 1; i < 24; ++i) o = o + pair[H + m - i] * v2f{fir[i], fir[i]};
-            v_lo = fmaxf(v_lo, fabsf(o.x));
-            v_hi = fmaxf(v_hi, fabsf(o.y));
+        float x_lo, x_hi, v_lo, v_hi;
+        run_values<DL>(w, pair, fir, m, x_lo, x_hi, v_lo, v_hi);
+        if constexpr (KEEP) {
+            v_all[m] = v_lo;
+            v_all[m + HALF] = v_hi;
         }
-        // strictly greater, in time order: the first frame of the maximum.  A NaN (every operand of the max was one) compares false.
-        if (in_lo && v_lo > t_lo) {
-            t_lo = v_lo;
-            kt_lo = (uint32_t)m;
-        }
-        if (in_hi && v_hi > t_hi) {
-            t_hi = v_hi;
-            kt_hi = (uint32_t)(m + HALF);
-        }
-        if (in_lo && x_lo > s_lo) {
-            s_lo = x_lo;
-            ks_lo = (uint32_t)m;
-        }
-        if (in_hi && x_hi > s_hi) {
-            s_hi = x_hi;
-            ks_hi = (uint32_t)(m + HALF);
-        }
+        t_lo.take(in_lo, v_lo, (uint32_t)m);
+        t_hi.take(in_hi, v_hi, (uint32_t)(m + HALF));
+        s_lo.take(in_lo, x_lo, (uint32_t)m);
+        s_hi.take(in_hi, x_hi, (uint32_t)(m + HALF));
     }
-    const bool t_newer = t_hi > t_lo, s_newer = s_hi > s_lo;  // the older half wins among equals
-    tp = t_newer ? t_hi : t_lo;
-    k_tp = t_newer ? kt_hi : kt_lo;
-    sp = s_newer ? s_hi : s_lo;
-    k_sp = s_newer ? ks_hi : ks_lo;
+    const PkFirstMax t = t_lo.then(t_hi), s = s_lo.then(s_hi);
+    tp = t.v;
+    k_tp = t.k;
+    sp = s.v;
+    k_sp = s.k;
 }
 
-template <int DL>
-__global__ __launch_bounds__(kThreads) void pk_tile_kernel(PkArgs a) {
+// A run that a segment boundary cuts (the timeline form): samples [0, n_a) lie before it, [n_a, n_here) behind it, and each side has
+// maxima of its own.  From the v the interpolator has formed (it does not run again) and |x|, in time order.
+__device__ __forceinline__ void run_sides(const float (&v_all)[R], const float* x, uint32_t n_a, uint32_t n_here, PkFirstMax (&t)[2], PkFirstMax (&s)[2]) {
+#pragma unroll
+    for (uint32_t n = 0; n < R; ++n) {
+        const bool before = n < n_a, behind = !before && n < n_here;
+        const float m = fabsf(x[n]);
+        t[0].take(before, v_all[n], n);
+        t[1].take(behind, v_all[n], n);
+        s[0].take(before, m, n);
+        s[1].take(behind, m, n);
+    }
+}
+
+// TL: the timeline form (program_peak_timeline.hpp), launched only with the timeline on: besides the partial it merges the maxima of
+// every segment the tile touches into the stream's keys.  Frame n of the call lies in segment seg_base + (phase + n) / L, and L >= 336
+// (kPlMinRate), so a run of 16 frames touches at most 2 segments and a tile at most 5.
+// Three wavefronts per SIMD are asked for: the timeline forms keep a run's sixteen v in registers beside the taps, and without the
+// bound the 4x / 2x ones come out at 169 / 172 VGPRs, one and four above what three wavefronts leave each (168).  With it they take
+// 167 / 168 and no scratch; the plain forms have the figures they had without it (152 / 143 / 55 VGPRs, 105 / 105 / 102 SGPRs).
+// The attribute is a minimum only and carries no upper bound: the sample-peak-only forms still reach their 7 / 6 wavefronts.
+template <int DL, bool TL>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) void pk_tile_kernel(PkArgs a) {
     extern __shared__ float lds[];  // [channels][kChanStride], then the taps
     constexpr int H = DL > 1 ? DL - 1 : 0;
     const uint32_t s = blockIdx.x / a.n_tiles, tile = blockIdx.x % a.n_tiles, tid = threadIdx.x;
@@ -184,10 +228,9 @@ __global__ __launch_bounds__(kThreads) void pk_tile_kernel(PkArgs a) {
         const uint32_t c = u >> 6, run = u & 63u;  // (c is uniform over the wavefront)
         const uint32_t first = run * R;
         const uint32_t n_here = nf > first ? min(nf - first, R) : 0u;
-        float tp = 0.0f, sp = 0.0f;
-        uint32_t k_tp = 0, k_sp = 0;
+        const uint32_t at = (uint32_t)start + first;  // frames of the call fit 32 bits (frames_capacity <= 2^32 - 1)
+        float w[R + H];
         if (n_here != 0) {
-            float w[R + H];
             const float* p = lds + c * kChanStride + 17u * run;
 #pragma unroll
             for (int k = -H; k < (int)R; ++k) {
@@ -195,10 +238,72 @@ __global__ __launch_bounds__(kThreads) void pk_tile_kernel(PkArgs a) {
                 constexpr int base = (int)kHalo;
                 w[k + H] = p[(base + k) + ((base + k) >> 4)];
             }
-            run_peaks<DL>(w, n_here, fir, tp, k_tp, sp, k_sp);
         }
-        const uint32_t at = (uint32_t)start + first;  // frames of the call fit 32 bits (frames_capacity <= 2^32 - 1)
-        const unsigned long long kt = wave_max(peak_key(tp, at + k_tp)), ks = wave_max(peak_key(sp, at + k_sp));
+        unsigned long long kt, ks;
+        if constexpr (!TL) {
+            float tp = 0.0f, sp = 0.0f;
+            uint32_t k_tp = 0, k_sp = 0;
+            if (n_here != 0) run_peaks<DL>(w, n_here, fir, tp, k_tp, sp, k_sp);
+            kt = wave_max(peak_key(tp, at + k_tp));
+            ks = wave_max(peak_key(sp, at + k_sp));
+        } else {
+            PkFirstMax t[2], m[2];
+            float v_all[R];
+            if (n_here != 0) run_peaks<DL, true>(w, n_here, fir, t[0].v, t[0].k, m[0].v, m[0].k, v_all);
+            // frame 0 of the tile is frame off0 of segment seg0, and the tile touches n_segs segments.  (Uniform; formed behind the
+            // interpolator, where the registers are free again; the 32-bit division is the common case and the cheap one.)
+            const uint32_t L = a.seg;
+            const uint64_t tile_pos = (uint64_t)call.phase + start;
+            uint32_t off0;
+            uint64_t seg0;
+            if ((tile_pos >> 32) == 0) {
+                seg0 = call.seg_base + (uint32_t)tile_pos / L;
+                off0 = (uint32_t)tile_pos % L;
+            } else {
+                seg0 = call.seg_base + tile_pos / L;
+                off0 = (uint32_t)(tile_pos % L);
+            }
+            const uint32_t n_segs = (off0 + nf - 1) / L + 1;
+            // the run starts at frame `pos` of segment `r` of the tile; n_a of its frames lie before its one possible boundary
+            uint32_t pos = off0 + first, r = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)  // (off0 + first < L + T <= 5 L)
+                if (pos >= L) {
+                    pos -= L;
+                    ++r;
+                }
+            const uint32_t n_a = min(n_here, L - pos);
+            // a boundary cuts the run of a few lanes per tile at most: only their wavefronts redo the bookkeeping, per side
+            if (__any(n_a < n_here) != 0 && n_here != 0) {
+                t[0] = m[0] = PkFirstMax{};
+                run_sides(v_all, w + H, n_a, n_here, t, m);
+            }
+            kt = 0ull;
+            ks = 0ull;
+            for (uint32_t q = 0; q < n_segs; ++q) {  // (uniform) segment q of the tile: the wavefront's maximum, then one atomic per kind
+                const bool mine_a = n_here != 0 && q == r, mine_b = n_a < n_here && q == r + 1;
+                unsigned long long qt = 0ull, qs = 0ull;
+                if (mine_a) {
+                    qt = peak_key(t[0].v, at + t[0].k);
+                    qs = peak_key(m[0].v, at + m[0].k);
+                } else if (mine_b) {
+                    qt = peak_key(t[1].v, at + t[1].k);
+                    qs = peak_key(m[1].v, at + m[1].k);
+                }
+                qt = wave_max(qt);
+                qs = wave_max(qs);
+                kt = qt > kt ? qt : kt;  // the tile's partial is the maximum over its segments
+                ks = qs > ks ? qs : ks;
+                // lane 0 the true peak, lane 1 the sample peak.  A maximum of 0 leaves the key as it is: cleared, a peak of 0 at offset 0.
+                const unsigned long long key = run == 0 ? qt : qs;
+                const uint64_t row = seg0 + q;
+                if (run < 2 && (key >> 32) != 0 && row < a.tl_rows) {
+                    const uint32_t in_tile = (0xFFFFFFFFu - (uint32_t)key) - (uint32_t)start;
+                    const unsigned long long merged = (key & 0xFFFFFFFF00000000ull) | (unsigned long long)(0xFFFFFFFFu - (off0 + in_tile - q * L));
+                    atomicMax(a.tl_keys + (((uint64_t)s * a.tl_rows + row) * C + c) * 2 + run, merged);
+                }
+            }
+        }
         if (run == 0) {
             PkPartial out;
             out.true_peak = __uint_as_float((uint32_t)(kt >> 32));
@@ -314,9 +419,15 @@ void launch_pk_tiles(const PkArgs& a, hipStream_t stream) {
     if (blocks > 0x7FFFFFFFull) unsupported("programme peaks: call too long for one launch");
     const size_t lds = ((size_t)a.channels * kChanStride + 36) * sizeof(float);
     const dim3 grid((uint32_t)blocks), block(64u * std::min(a.channels, kThreads / 64u));
-    if (a.delay_len == 12) hipLaunchKernelGGL(pk_tile_kernel<12>, grid, block, lds, stream, a);
-    else if (a.delay_len == 24) hipLaunchKernelGGL(pk_tile_kernel<24>, grid, block, lds, stream, a);
-    else hipLaunchKernelGGL(pk_tile_kernel<0>, grid, block, lds, stream, a);
+    if (a.tl_keys) {  // the timeline form: only a bank with the peak timeline on runs these
+        if (a.delay_len == 12) hipLaunchKernelGGL((pk_tile_kernel<12, true>), grid, block, lds, stream, a);
+        else if (a.delay_len == 24) hipLaunchKernelGGL((pk_tile_kernel<24, true>), grid, block, lds, stream, a);
+        else hipLaunchKernelGGL((pk_tile_kernel<0, true>), grid, block, lds, stream, a);
+        return;
+    }
+    if (a.delay_len == 12) hipLaunchKernelGGL((pk_tile_kernel<12, false>), grid, block, lds, stream, a);
+    else if (a.delay_len == 24) hipLaunchKernelGGL((pk_tile_kernel<24, false>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((pk_tile_kernel<0, false>), grid, block, lds, stream, a);
 }
 void launch_pk_fold(const PkArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(pk_fold_kernel, dim3(a.n_streams), dim3(64 * kPlSlots), 0, stream, a);

@@ -187,6 +187,35 @@ def evaluate_gain(api: Api, rule: GainRule, integrated_lufs: float, gating_above
     return out[0]
 
 
+# ---- include/omx/program_peak_timeline.h
+_u32x8 = C.c_uint32 * 8
+
+
+class CProgramPeakRow(C.Structure):
+    """omx_program_peak_row (include/omx/program_peak_timeline.h)"""
+    _fields_ = [("true_peak", _f32x8), ("sample_peak", _f32x8), ("true_peak_offset", _u32x8), ("sample_peak_offset", _u32x8),
+                ("frames", C.c_uint32), ("valid", C.c_uint32)]
+
+
+class CProgramPartPeak(C.Structure):
+    """omx_program_part_peak (include/omx/program_peak_timeline.h)"""
+    _fields_ = [("frames", C.c_uint64), ("true_peak_frame", _u64x8), ("sample_peak_frame", _u64x8), ("true_peak_member", _u32x8),
+                ("sample_peak_member", _u32x8), ("true_peak", _f32x8), ("sample_peak", _f32x8), ("true_peak_db", _f32x8),
+                ("sample_peak_db", _f32x8), ("max_true_peak_db", C.c_float), ("max_sample_peak_db", C.c_float),
+                ("max_true_peak_channel", C.c_uint32), ("channels", C.c_uint32)]
+
+
+PEAK_ROW_DTYPE = np.dtype([("true_peak", "<f4", (8,)), ("sample_peak", "<f4", (8,)), ("true_peak_offset", "<u4", (8,)),
+                           ("sample_peak_offset", "<u4", (8,)), ("frames", "<u4"), ("valid", "<u4")])
+PART_PEAK_DTYPE = np.dtype([("frames", "<u8"), ("true_peak_frame", "<u8", (8,)), ("sample_peak_frame", "<u8", (8,)),
+                            ("true_peak_member", "<u4", (8,)), ("sample_peak_member", "<u4", (8,)), ("true_peak", "<f4", (8,)),
+                            ("sample_peak", "<f4", (8,)), ("true_peak_db", "<f4", (8,)), ("sample_peak_db", "<f4", (8,)),
+                            ("max_true_peak_db", "<f4"), ("max_sample_peak_db", "<f4"), ("max_true_peak_channel", "<u4"),
+                            ("channels", "<u4")])
+assert C.sizeof(CProgramPeakRow) == 136 and C.sizeof(CProgramPartPeak) == 344
+assert PEAK_ROW_DTYPE.itemsize == 136 and PART_PEAK_DTYPE.itemsize == 344
+
+
 class CProgramLimitRule(C.Structure):
     """omx_program_limit_rule (include/omx/program_limit.h)"""
     _fields_ = [("ceiling_db", C.c_float), ("attack_frames", C.c_uint32), ("release_hold_frames", C.c_uint32), ("flags", C.c_uint32)]
@@ -922,6 +951,84 @@ class ProgramLoudnessBank:
         self.api.check(self.api.fn("program_loudness_bank_fetch_gains", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p])(
             self._h, first, count, out.ctypes.data if count else None))
         return out
+
+    # ---- include/omx/program_peak_timeline.h
+    def set_peak_timeline(self, on: bool = True):
+        """Keep true peak and sample peak per 100 ms segment as well (include/omx/program_peak_timeline.h); off by default.  Needs
+        set_peaks(True), and only while no stream holds samples.  set_peaks(False) switches it off too."""
+        self.api.check(self.api.fn("program_loudness_bank_set_peak_timeline", C.c_int, [C.c_void_p, C.c_uint32])(self._h, 1 if on else 0))
+
+    def peak_rows(self, d_rows: int, first: int = 0, stride: int = 1, count: int = 0, stream: int = 0) -> int:
+        """Row i < count of every stream = the peaks over the segments [first + i * stride, first + (i + 1) * stride), into the device
+        buffer d_rows: omx_program_peak_row [n_streams][count] (PEAK_ROW_DTYPE, 136 bytes each), enqueued on `stream`."""
+        f = self.api.fn("program_loudness_bank_peak_rows", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p])
+        return self.api.check(f(self._h, first, stride, count, C.c_void_p(d_rows or 0), C.c_void_p(stream or 0)))
+
+    def fetch_peak_rows(self, stream_index: int, first: int = 0, stride: int = 1, count: Optional[int] = None) -> np.ndarray:
+        """The same rows of one stream as a PEAK_ROW_DTYPE array (count None: up to the stream's last frame, the open segment
+        included); synchronises."""
+        if count is None:
+            frames = int(self.fetch_peaks(stream_index).frames)
+            segments = 1 if frames else 0   # no complete segment yet: everything lies in the open one
+            if int(self.fetch(stream_index).segments):
+                length = int(self.fetch_peak_rows(stream_index, 0, 1, 1)[0]["frames"])   # row 0 is a complete segment: its frames are L
+                segments = (frames + length - 1) // length
+            count = (segments - first + stride - 1) // stride if stride > 0 and segments > first else 0
+        out = np.zeros((max(count, 0),), PEAK_ROW_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_peak_rows", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, stream_index, first, stride, count, out.ctypes.data if count else None))
+        return out
+
+    def measure_interval_peaks(self, intervals, stream: int = 0) -> int:
+        """The peaks of every interval (stream, first_segment, segment_count; the count may be TO_END), on `stream`; returns the device
+        pointer to omx_program_part_peak[n] (0 for no interval), valid until the next call on the bank."""
+        arr = self._intervals(intervals)
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_measure_interval_peaks", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, arr.ctypes.data if len(arr) else None, len(arr), C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_interval_peaks(self, intervals) -> np.ndarray:
+        """The same records as a PART_PEAK_DTYPE array; synchronises."""
+        arr = self._intervals(intervals)
+        out = np.zeros((len(arr),), PART_PEAK_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_interval_peaks", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, arr.ctypes.data if len(arr) else None, len(arr), out.ctypes.data if len(arr) else None))
+        return out
+
+    def measure_group_peaks(self, members, groups, stream: int = 0) -> int:
+        """The peaks of every group of members (tables as for measure_groups), on `stream`; returns the device pointer to
+        omx_program_part_peak[n_groups] (0 for no group), valid until the next call on the bank."""
+        m, g = self._intervals(members), self._groups(groups)
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_measure_group_peaks", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_group_peaks(self, members, groups) -> np.ndarray:
+        """The same records as a PART_PEAK_DTYPE array, one per group; synchronises."""
+        m, g = self._intervals(members), self._groups(groups)
+        out = np.zeros((len(g),), PART_PEAK_DTYPE)
+        f = self.api.fn("program_loudness_bank_fetch_group_peaks", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p])
+        self.api.check(f(self._h, m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         out.ctypes.data if len(g) else None))
+        return out
+
+    def plan_part_gains(self, rule: GainRule, members, groups, stream: int = 0) -> int:
+        """plan_group_gains with the true peak of the group's own segments (the peak timeline) as the source peak, not that of the
+        members' whole streams.  Same records, buffer and fetch_gains."""
+        m, g = self._intervals(members), self._groups(groups)
+        out, c = C.c_void_p(), rule.to_c()
+        f = self.api.fn("program_loudness_bank_plan_part_gains", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.byref(c), m.ctypes.data if len(m) else None, len(m), g.ctypes.data if len(g) else None, len(g),
+                         C.c_void_p(stream or 0), C.byref(out)))
+        if len(g):
+            self._planned = len(g)
+        return out.value or 0
 
     def apply_gains(self, d_in: int, d_out: int, frames_capacity: int, channels: int, d_gains: int, n_gains: int,
                     frames: Optional[Sequence[int]] = None, gain_of_stream: Optional[Sequence[int]] = None, stream: int = 0) -> int:
