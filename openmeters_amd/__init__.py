@@ -44,6 +44,11 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_edit.h)
     EditClip, TrimRule, edit_curve, edit_extent, edit_gain, edit_plan, edit_table, edit_trim)
 from .program_loudness import (  # noqa: F401  (include/omx/program_peak_timeline.h)
     PART_PEAK_DTYPE, PEAK_ROW_DTYPE, CProgramPartPeak, CProgramPeakRow)
+from .program_loudness import (  # noqa: F401  (include/omx/program_filter.h)
+    FILTER_BYPASS, FILTER_DC_BLOCK, FILTER_DEEMPHASIS, FILTER_DTYPE, FILTER_HIGH_SHELF, FILTER_HIGHPASS, FILTER_INFO_DTYPE,
+    FILTER_LOW_SHELF, FILTER_LOWPASS, FILTER_MAX_FILTERS, FILTER_MAX_SECTIONS, FILTER_NOTCH, FILTER_PEAKING, FILTER_PREEMPHASIS,
+    FILTER_RECORD_DTYPE, CProgramFilter, CProgramFilterInfo, CProgramFilterRecord, CProgramFilterSection, CProgramFilterSpec, FilterSpec,
+    filter_cascade, filter_check, filter_design, filter_plan, filter_response, filter_table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

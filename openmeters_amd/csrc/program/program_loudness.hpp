@@ -17,6 +17,7 @@
 #include "program_inspect.hpp"
 #include "program_edit.hpp"
 #include "program_peak_timeline.hpp"
+#include "program_filter.hpp"
 
 namespace omx {
 
@@ -174,6 +175,15 @@ public:
                           omx_program_part_peak* dst);
     int plan_part_gains(const omx_program_gain_rule* rule, const omx_program_interval* members, uint64_t n_members,
                         const omx_program_group* groups, uint64_t n_groups, hipStream_t stream, const omx_program_gain_record** d_gains);
+    // include/omx/program_filter.h (program_filter.cpp)
+    int filter_configure(uint32_t channels, double sample_rate, const omx_program_filter* filters, uint32_t n_filters,
+                         const uint32_t* filter_of_channel);
+    int filter_reset(const uint8_t* reset_mask);
+    int filter(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, hipStream_t stream,
+               const omx_program_filter_record** d_filtered);
+    int fetch_filtered(uint64_t stream_index, omx_program_filter_record* dst);
+    int filter_set_form(uint32_t form);
+    int filter_last_form() const { return filter_last_form_; }
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -279,6 +289,10 @@ private:
     std::unique_ptr<ProgramInspector> inspector_;
     // edit: nothing is allocated or launched until edit_configure
     std::unique_ptr<ProgramEdit> edit_;
+    // filter: nothing is allocated or launched until filter_configure
+    FlArgs filter_args() const;
+    std::unique_ptr<ProgramFilter> filter_;
+    int filter_form_ = 0, filter_last_form_ = 0;
 };
 
 }  // namespace omx

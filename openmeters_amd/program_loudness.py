@@ -717,6 +717,122 @@ def histogram_boundaries(api: Api) -> np.ndarray:
 FORM_BY_SHAPE, FORM_REFERENCE_ORDER, FORM_TIME_PARALLEL = 0, 1, 2
 
 
+class CProgramFilterSection(C.Structure):
+    """omx_program_filter_section (include/omx/program_filter.h)"""
+    _fields_ = [("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("a1", C.c_double), ("a2", C.c_double)]
+
+
+FILTER_MAX_SECTIONS = 2
+FILTER_MAX_FILTERS = 256
+FILTER_BYPASS = 0xFFFFFFFF
+# omx_program_filter_spec.kind
+(FILTER_HIGHPASS, FILTER_LOWPASS, FILTER_LOW_SHELF, FILTER_HIGH_SHELF, FILTER_PEAKING, FILTER_NOTCH, FILTER_DC_BLOCK, FILTER_DEEMPHASIS,
+ FILTER_PREEMPHASIS) = range(9)
+
+
+class CProgramFilter(C.Structure):
+    """omx_program_filter (include/omx/program_filter.h)"""
+    _fields_ = [("n_sections", C.c_uint32), ("_pad", C.c_uint32), ("section", CProgramFilterSection * FILTER_MAX_SECTIONS)]
+
+
+class CProgramFilterSpec(C.Structure):
+    """omx_program_filter_spec (include/omx/program_filter.h)"""
+    _fields_ = [("kind", C.c_uint32), ("order", C.c_uint32), ("frequency_hz", C.c_double), ("q", C.c_double), ("gain_db", C.c_double),
+                ("time_constant_us", C.c_double), ("time_constant_zero_us", C.c_double)]
+
+
+class CProgramFilterInfo(C.Structure):
+    """omx_program_filter_info (include/omx/program_filter.h)"""
+    _fields_ = [("chunk_frames", C.c_uint32), ("tile_frames", C.c_uint32), ("channels", C.c_uint32), ("streams_per_wavefront", C.c_uint32)]
+
+
+class CProgramFilterRecord(C.Structure):
+    """omx_program_filter_record (include/omx/program_filter.h)"""
+    _fields_ = [("frames", C.c_uint64), ("frames_total", C.c_uint64), ("samples_over", C.c_uint64), ("samples_nonfinite", C.c_uint64),
+                ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float), ("form", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+FILTER_SECTION_DTYPE = np.dtype([("b0", "<f8"), ("b1", "<f8"), ("b2", "<f8"), ("a1", "<f8"), ("a2", "<f8")])
+FILTER_DTYPE = np.dtype([("n_sections", "<u4"), ("_pad", "<u4"), ("section", FILTER_SECTION_DTYPE, (FILTER_MAX_SECTIONS,))])
+FILTER_INFO_DTYPE = np.dtype([("chunk_frames", "<u4"), ("tile_frames", "<u4"), ("channels", "<u4"), ("streams_per_wavefront", "<u4")])
+FILTER_RECORD_DTYPE = np.dtype([("frames", "<u8"), ("frames_total", "<u8"), ("samples_over", "<u8"), ("samples_nonfinite", "<u8"),
+                                ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"), ("form", "<u4"), ("_pad", "<u4")])
+assert C.sizeof(CProgramFilterSection) == 40 and C.sizeof(CProgramFilter) == 88 and C.sizeof(CProgramFilterSpec) == 48
+assert C.sizeof(CProgramFilterInfo) == 16 and C.sizeof(CProgramFilterRecord) == 48
+assert FILTER_DTYPE.itemsize == 88 and FILTER_INFO_DTYPE.itemsize == 16 and FILTER_RECORD_DTYPE.itemsize == 48
+
+
+@dataclass
+class FilterSpec:
+    """omx_program_filter_spec: the kind (FILTER_*), the order (FILTER_HIGHPASS / FILTER_LOWPASS: 1, 2 or 4), the corner or centre
+    frequency, q (0: 1/sqrt(2)), the gain of a shelf or peak, and for the emphasis kinds the time constant in microseconds with the
+    other one of a pair (50 / 15) as time_constant_zero_us."""
+    kind: int = FILTER_HIGHPASS
+    order: int = 0
+    frequency_hz: float = 0.0
+    q: float = 0.0
+    gain_db: float = 0.0
+    time_constant_us: float = 0.0
+    time_constant_zero_us: float = 0.0
+
+    def to_c(self) -> CProgramFilterSpec:
+        return CProgramFilterSpec(self.kind, self.order, self.frequency_hz, self.q, self.gain_db, self.time_constant_us,
+                                  self.time_constant_zero_us)
+
+
+def filter_table(filters) -> np.ndarray:
+    """Filters as a contiguous FILTER_DTYPE array: one FILTER_DTYPE scalar or array, or a sequence whose entries are FILTER_DTYPE
+    scalars or lists of one or two (b0, b1, b2, a1, a2)."""
+    if isinstance(filters, np.ndarray) and filters.dtype == FILTER_DTYPE:
+        return np.ascontiguousarray(filters).reshape(-1)
+    out = np.zeros((len(filters),), FILTER_DTYPE)
+    for k, f in enumerate(filters):
+        if isinstance(f, (np.ndarray, np.void)) and f.dtype == FILTER_DTYPE:
+            out[k] = f
+        else:
+            out[k]["n_sections"] = len(f)
+            for i, sec in enumerate(list(f)[:FILTER_MAX_SECTIONS]):
+                out[k]["section"][i] = tuple(sec)
+    return out
+
+
+def filter_design(api: Api, spec: FilterSpec, sample_rate: float) -> np.ndarray:
+    """The filter of a spec at a sample rate (omx_program_filter_design) as a FILTER_DTYPE scalar.  Needs no device."""
+    out, c = np.zeros((1,), FILTER_DTYPE), spec.to_c()
+    api.check(api.fn("program_filter_design", C.c_int, [C.c_void_p, C.c_double, C.c_void_p])(C.byref(c), sample_rate, out.ctypes.data))
+    return out[0]
+
+
+def filter_cascade(api: Api, a, b) -> np.ndarray:
+    """The sections of a, then those of b (omx_program_filter_cascade) as a FILTER_DTYPE scalar.  Needs no device."""
+    fa, fb, out = filter_table([a]), filter_table([b]), np.zeros((1,), FILTER_DTYPE)
+    api.check(api.fn("program_filter_cascade", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])(fa.ctypes.data, fb.ctypes.data, out.ctypes.data))
+    return out[0]
+
+
+def filter_check(api: Api, filt) -> int:
+    """0 for a filter the bank takes (omx_program_filter_check); raises OmxError with status -3 for an invalid one, -2 for one that is
+    not strictly stable.  Needs no device."""
+    f = filter_table([filt])
+    return api.check(api.fn("program_filter_check", C.c_int, [C.c_void_p])(f.ctypes.data))
+
+
+def filter_response(api: Api, filt, sample_rate: float, frequency_hz: float):
+    """(magnitude in dB, phase in radians) of H(e^{jw}) (omx_program_filter_response).  Needs no device."""
+    f, mag, ph = filter_table([filt]), C.c_double(), C.c_double()
+    api.check(api.fn("program_filter_response", C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p])(
+        f.ctypes.data, sample_rate, frequency_hz, C.byref(mag), C.byref(ph)))
+    return mag.value, ph.value
+
+
+def filter_plan(api: Api, channels: int, sample_rate: float) -> np.ndarray:
+    """The plan of a channel count and rate (omx_program_filter_plan) as a FILTER_INFO_DTYPE scalar: the work item of the
+    time-parallel form and the kernels' tile, in frames.  Needs no device."""
+    out = np.zeros((1,), FILTER_INFO_DTYPE)
+    api.check(api.fn("program_filter_plan", C.c_int, [C.c_uint32, C.c_double, C.c_void_p])(channels, sample_rate, out.ctypes.data))
+    return out[0]
+
+
 class ProgramLoudnessBank:
     """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
 
@@ -1244,6 +1360,55 @@ class ProgramLoudnessBank:
         self.api.check(self.api.fn("program_loudness_bank_fetch_inspected", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
+
+    # ---- include/omx/program_filter.h
+    def configure_filter(self, filters, channels: int, sample_rate: float, filter_of_channel=None):
+        """Set the filter table (see filter_table), the channel count and the rate of the PCM the filter stage takes, and which filter
+        every channel runs: filter_of_channel [n_streams][channels] of table indices or FILTER_BYPASS, None: filter 0 everywhere.
+        Builds the tables of the time-parallel form, allocates state and records and resets every stream.  Only while no stream
+        holds filter state: a new bank, or after reset_filter() of every stream."""
+        table = filter_table(filters)
+        foc = None
+        if filter_of_channel is not None:
+            foc = np.ascontiguousarray(filter_of_channel, np.uint32).reshape(-1)
+            if foc.size != self.n_streams * channels:
+                raise ValueError(f"filter_of_channel: {foc.size} entries for {self.n_streams} streams of {channels} channels")
+        self.api.check(self.api.fn("program_loudness_bank_filter_configure", C.c_int,
+                                   [C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_uint32, C.c_void_p])(
+            self._h, channels, sample_rate, table.ctypes.data if table.size else None, table.size, foc.ctypes.data if foc is not None else None))
+
+    def reset_filter(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the filter stage start over with zero state and a zero record (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_filter_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def filter(self, d_in: int, d_out: int, frames_capacity: int, frames: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """d_out[s][f][c] = d_in[s][f][c] through the filter of channel c of stream s, for f < frames[s], on `stream`; both f32
+        [n_streams][frames_capacity][channels].  d_out == d_in filters in place; no float beyond a stream's frames is written.
+        Returns the device pointer to omx_program_filter_record[n_streams] (FILTER_RECORD_DTYPE), written fresh by every call."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_filter", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(d_out or 0),
+                         C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_filtered(self, stream_index: int) -> np.ndarray:
+        """One stream's record of the last filter call as a FILTER_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), FILTER_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_filtered", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    def set_filter_form(self, form: int):
+        """0 = by call shape, 1 = reference order, 2 = time-parallel, for filter() alone."""
+        self.api.check(self.api.fn("program_loudness_bank_filter_set_form", C.c_int, [C.c_void_p, C.c_uint32])(self._h, form))
+
+    def last_filter_form(self) -> int:
+        """1 = the last filter call ran in reference order, 2 = in the time-parallel form, 0 = none yet."""
+        return self.api.fn("debug_program_loudness_bank_filter_last_form", C.c_int, [C.c_void_p])(self._h)
 
     # ---- include/omx/program_edit.h
     def configure_edit(self, channels: int, max_outputs: int):
