@@ -49,6 +49,9 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_filter.h)
     FILTER_LOW_SHELF, FILTER_LOWPASS, FILTER_MAX_FILTERS, FILTER_MAX_SECTIONS, FILTER_NOTCH, FILTER_PEAKING, FILTER_PREEMPHASIS,
     FILTER_RECORD_DTYPE, CProgramFilter, CProgramFilterInfo, CProgramFilterRecord, CProgramFilterSection, CProgramFilterSpec, FilterSpec,
     filter_cascade, filter_check, filter_design, filter_plan, filter_response, filter_table)
+from .program_loudness import (  # noqa: F401  (include/omx/program_mix.h)
+    MIX_INFO_DTYPE, MIX_MAX_BUSES, MIX_MAX_LAYERS, MIX_MAX_POSITION, MIX_MAX_SENDS, MIX_RECORD_DTYPE, MIX_SEND_DTYPE, CProgramMixInfo,
+    CProgramMixRecord, CProgramMixSend, MixSend, mix_extent, mix_null, mix_plan, mix_table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

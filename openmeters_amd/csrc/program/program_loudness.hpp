@@ -18,6 +18,7 @@
 #include "program_edit.hpp"
 #include "program_peak_timeline.hpp"
 #include "program_filter.hpp"
+#include "program_mix.hpp"
 
 namespace omx {
 
@@ -184,6 +185,12 @@ public:
     int fetch_filtered(uint64_t stream_index, omx_program_filter_record* dst);
     int filter_set_form(uint32_t form);
     int filter_last_form() const { return filter_last_form_; }
+    // include/omx/program_mix.h (program_mix.cpp)
+    int mix_configure(uint32_t channels, uint32_t max_buses);
+    int mix(const float* d_in, uint64_t frames_capacity, const uint32_t* frames_in, const omx_program_mix_send* sends, uint64_t n_sends,
+            float* d_out, uint64_t out_capacity, uint32_t n_out, const uint64_t* out_first, const uint32_t* out_frames, hipStream_t stream,
+            const omx_program_mix_record** d_mixed);
+    int fetch_mixed(uint64_t bus, omx_program_mix_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -293,6 +300,8 @@ private:
     FlArgs filter_args() const;
     std::unique_ptr<ProgramFilter> filter_;
     int filter_form_ = 0, filter_last_form_ = 0;
+    // mix: nothing is allocated or launched until mix_configure
+    std::unique_ptr<ProgramMix> mix_;
 };
 
 }  // namespace omx

@@ -678,6 +678,91 @@ def edit_trim(api: Api, record: np.ndarray, rule: TrimRule, src_stream: int = 0,
     return EditClip(*[int(row[f]) for f in EDIT_CLIP_DTYPE.names[:-1]], float(row["gain"])), int(total.value)
 
 
+class CProgramMixSend(C.Structure):
+    """omx_program_mix_send (include/omx/program_mix.h)"""
+    _fields_ = [("src_stream", C.c_uint32), ("dst_bus", C.c_uint32), ("src_first", C.c_uint64), ("dst_first", C.c_uint64),
+                ("frames", C.c_uint64), ("gain", C.c_float), ("flags", C.c_uint32)]
+
+
+class CProgramMixInfo(C.Structure):
+    """omx_program_mix_info (include/omx/program_mix.h)"""
+    _fields_ = [("tile_frames", C.c_uint32), ("layers_per_batch", C.c_uint32), ("channels", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramMixRecord(C.Structure):
+    """omx_program_mix_record (include/omx/program_mix.h)"""
+    _fields_ = [("out_first", C.c_uint64), ("frames", C.c_uint64), ("silent_frames", C.c_uint64), ("mixed_frames", C.c_uint64),
+                ("samples_over", C.c_uint64), ("samples_nonfinite", C.c_uint64), ("out_sample_peak", C.c_float),
+                ("out_sample_peak_db", C.c_float), ("sends", C.c_uint32), ("max_layers", C.c_uint32)]
+
+
+MIX_SEND_DTYPE = np.dtype([("src_stream", "<u4"), ("dst_bus", "<u4"), ("src_first", "<u8"), ("dst_first", "<u8"), ("frames", "<u8"),
+                           ("gain", "<f4"), ("flags", "<u4")])
+MIX_INFO_DTYPE = np.dtype([("tile_frames", "<u4"), ("layers_per_batch", "<u4"), ("channels", "<u4"), ("_pad", "<u4")])
+MIX_RECORD_DTYPE = np.dtype([("out_first", "<u8"), ("frames", "<u8"), ("silent_frames", "<u8"), ("mixed_frames", "<u8"),
+                             ("samples_over", "<u8"), ("samples_nonfinite", "<u8"), ("out_sample_peak", "<f4"),
+                             ("out_sample_peak_db", "<f4"), ("sends", "<u4"), ("max_layers", "<u4")])
+assert C.sizeof(CProgramMixSend) == 40 and C.sizeof(CProgramMixInfo) == 16 and C.sizeof(CProgramMixRecord) == 64
+assert MIX_SEND_DTYPE.itemsize == 40 and MIX_INFO_DTYPE.itemsize == 16 and MIX_RECORD_DTYPE.itemsize == 64
+MIX_MAX_LAYERS = 64
+MIX_MAX_SENDS = 1 << 20
+MIX_MAX_BUSES = 1 << 24
+MIX_MAX_POSITION = 1 << 40
+
+
+@dataclass
+class MixSend:
+    """omx_program_mix_send: source frames [src_first, src_first + frames) of input stream src_stream land at frames
+    [dst_first, dst_first + frames) of bus dst_bus, times gain (negative: inverted polarity)"""
+    src_stream: int = 0
+    dst_bus: int = 0
+    src_first: int = 0
+    dst_first: int = 0
+    frames: int = 0
+    gain: float = 1.0
+    flags: int = 0
+
+    def to_row(self) -> tuple:
+        return (self.src_stream, self.dst_bus, self.src_first, self.dst_first, self.frames, self.gain, self.flags)
+
+
+def mix_table(sends) -> np.ndarray:
+    """A send table as a contiguous MIX_SEND_DTYPE array, from a sequence of MixSend or from such an array"""
+    if isinstance(sends, np.ndarray):
+        return np.ascontiguousarray(sends, MIX_SEND_DTYPE).reshape(-1)
+    return np.array([s.to_row() for s in sends], MIX_SEND_DTYPE).reshape(-1)
+
+
+def mix_plan(api: Api, channels: int) -> np.ndarray:
+    """The plan of a channel count (omx_program_mix_plan) as a MIX_INFO_DTYPE scalar: the main kernel's tile in bus frames and the
+    layers whose loads it keeps in flight together.  Needs no device."""
+    out = np.zeros((1,), MIX_INFO_DTYPE)
+    api.check(api.fn("program_mix_plan", C.c_int, [C.c_uint32, C.c_void_p])(channels, out.ctypes.data))
+    return out[0]
+
+
+def mix_extent(api: Api, sends, frames_in: Sequence[int], n_out: int) -> np.ndarray:
+    """Validate a send table against the frames of the input streams (omx_program_mix_extent) -> uint64 [n_out]: one past the last
+    covered frame of every bus.  Needs no device."""
+    table = mix_table(sends)
+    fr = np.ascontiguousarray(frames_in, np.uint32).reshape(-1)
+    out = np.zeros((n_out,), np.uint64)
+    api.check(api.fn("program_mix_extent", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])(
+        table.ctypes.data if table.size else None, table.size, fr.size, fr.ctypes.data if fr.size else None, n_out,
+        out.ctypes.data if n_out else None))
+    return out
+
+
+def mix_null(api: Api, stems: Sequence[int], reference_stream: int, frames: int, bus: int = 0) -> np.ndarray:
+    """The table of a null test (omx_program_mix_null) as a MIX_SEND_DTYPE array: every stem at +1, then the reference at -1, over
+    frames [0, frames) of `bus`.  Needs no device."""
+    st = np.ascontiguousarray(stems, np.uint32).reshape(-1)
+    out = np.zeros((st.size + 1,), MIX_SEND_DTYPE)
+    api.check(api.fn("program_mix_null", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p])(
+        st.ctypes.data if st.size else None, st.size, reference_stream, frames, bus, out.ctypes.data))
+    return out
+
+
 HISTOGRAM_BINS, HISTOGRAM_TAIL = 1000, 29
 _u64xbins, _f64xbins = C.c_uint64 * HISTOGRAM_BINS, C.c_double * HISTOGRAM_BINS
 
@@ -1445,4 +1530,42 @@ class ProgramLoudnessBank:
         out = np.zeros((1,), EDIT_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_edited", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, output_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_mix.h
+    def configure_mix(self, channels: int, max_buses: int):
+        """Set the channel count of the PCM the mix pass takes and the largest number of buses of a call; allocates the records.
+        Allowed at any time; mix calls still enqueued are waited for."""
+        self.api.check(self.api.fn("program_loudness_bank_mix_configure", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32])(
+            self._h, channels, max_buses))
+
+    def mix(self, d_in: int, frames_capacity: int, sends, d_out: int, out_capacity: int, out_frames: Sequence[int],
+            out_first: Optional[Sequence[int]] = None, frames_in: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Render the send table (a sequence of MixSend or a MIX_SEND_DTYPE array, sorted by (dst_bus, dst_first)) from d_in (f32
+        [n_streams][frames_capacity][channels]; frames_in[s]: the frames stream s holds, None: the whole row) into d_out (f32
+        [len(out_frames)][out_capacity][channels]) on `stream`: bus frames [out_first[o], out_first[o] + out_frames[o]) of bus o land
+        at d_out[o][0 ..]; out_first None: 0.  Up to 64 sends over a frame are summed in f64 in table order and rounded once.  Out of
+        place; no float beyond a window is written.  Returns the device pointer to omx_program_mix_record[max_buses]
+        (MIX_RECORD_DTYPE), entries below len(out_frames) written fresh by every call."""
+        table = mix_table(sends)
+        fr = self._per_stream(frames_in, np.uint32, "frames_in")
+        of = np.ascontiguousarray(out_frames, np.uint32).reshape(-1)
+        first = None if out_first is None else np.ascontiguousarray(out_first, np.uint64).reshape(-1)
+        if first is not None and first.size != of.size:
+            raise ValueError(f"out_first: {first.size} entries for {of.size} buses")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_mix", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
+                         C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                         table.ctypes.data if table.size else None, table.size, C.c_void_p(d_out or 0), out_capacity, of.size,
+                         first.ctypes.data if first is not None else None, of.ctypes.data if of.size else None, C.c_void_p(stream or 0),
+                         C.byref(out)))
+        return out.value or 0
+
+    def fetch_mixed(self, bus: int) -> np.ndarray:
+        """One bus's record of the last mix call as a MIX_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), MIX_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_mixed", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, bus, out.ctypes.data))
         return out[0]
