@@ -52,6 +52,11 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_filter.h)
 from .program_loudness import (  # noqa: F401  (include/omx/program_mix.h)
     MIX_INFO_DTYPE, MIX_MAX_BUSES, MIX_MAX_LAYERS, MIX_MAX_POSITION, MIX_MAX_SENDS, MIX_RECORD_DTYPE, MIX_SEND_DTYPE, CProgramMixInfo,
     CProgramMixRecord, CProgramMixSend, MixSend, mix_extent, mix_null, mix_plan, mix_table)
+from .program_loudness import (  # noqa: F401  (include/omx/program_convolve.h)
+    CONVOLVE_BANDPASS, CONVOLVE_BANDSTOP, CONVOLVE_BYPASS, CONVOLVE_FLUSHED, CONVOLVE_HIGHPASS, CONVOLVE_IDLE, CONVOLVE_INFO_DTYPE,
+    CONVOLVE_LOWPASS, CONVOLVE_MAX_FIRS, CONVOLVE_MAX_TAPS, CONVOLVE_RECORD_DTYPE, CONVOLVE_RUNNING, ConvolveSpec, CProgramConvolveInfo,
+    CProgramConvolveRecord, CProgramConvolveSpec, CProgramFir, convolve_check, convolve_design, convolve_frames, convolve_plan,
+    convolve_response)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

@@ -19,6 +19,7 @@
 #include "program_peak_timeline.hpp"
 #include "program_filter.hpp"
 #include "program_mix.hpp"
+#include "program_convolve.hpp"
 
 namespace omx {
 
@@ -191,6 +192,13 @@ public:
             float* d_out, uint64_t out_capacity, uint32_t n_out, const uint64_t* out_first, const uint32_t* out_frames, hipStream_t stream,
             const omx_program_mix_record** d_mixed);
     int fetch_mixed(uint64_t bus, omx_program_mix_record* dst);
+    // include/omx/program_convolve.h (program_convolve.cpp)
+    int convolve_configure(uint32_t channels, const omx_program_fir* firs, uint32_t n_firs, const uint32_t* fir_of_channel,
+                           uint32_t delay_frames);
+    int convolve_reset(const uint8_t* reset_mask);
+    int convolve(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
+                 const uint8_t* flush_mask, hipStream_t stream, const omx_program_convolve_record** d_convolved);
+    int fetch_convolved(uint64_t stream_index, omx_program_convolve_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -302,6 +310,9 @@ private:
     int filter_form_ = 0, filter_last_form_ = 0;
     // mix: nothing is allocated or launched until mix_configure
     std::unique_ptr<ProgramMix> mix_;
+    // convolve: nothing is allocated or launched until convolve_configure
+    CvArgs convolve_args() const;
+    std::unique_ptr<ProgramConvolve> convolve_;
 };
 
 }  // namespace omx

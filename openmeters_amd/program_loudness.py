@@ -918,6 +918,103 @@ def filter_plan(api: Api, channels: int, sample_rate: float) -> np.ndarray:
     return out[0]
 
 
+class CProgramFir(C.Structure):
+    """omx_program_fir (include/omx/program_convolve.h)"""
+    _fields_ = [("taps", C.c_void_p), ("n_taps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CProgramConvolveSpec(C.Structure):
+    """omx_program_convolve_spec (include/omx/program_convolve.h)"""
+    _fields_ = [("kind", C.c_uint32), ("n_taps", C.c_uint32), ("f_lo_hz", C.c_double), ("f_hi_hz", C.c_double), ("beta", C.c_double)]
+
+
+class CProgramConvolveInfo(C.Structure):
+    """omx_program_convolve_info (include/omx/program_convolve.h)"""
+    _fields_ = [("tile_frames", C.c_uint32), ("frames_per_thread", C.c_uint32), ("tap_block", C.c_uint32), ("channels", C.c_uint32)]
+
+
+class CProgramConvolveRecord(C.Structure):
+    """omx_program_convolve_record (include/omx/program_convolve.h)"""
+    _fields_ = [("frames_in", C.c_uint64), ("frames_out", C.c_uint64), ("frames_written", C.c_uint64), ("samples_over", C.c_uint64),
+                ("samples_nonfinite", C.c_uint64), ("out_sample_peak", C.c_float), ("out_sample_peak_db", C.c_float),
+                ("state", C.c_uint32), ("delay_frames", C.c_uint32), ("max_taps", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+CONVOLVE_INFO_DTYPE = np.dtype([("tile_frames", "<u4"), ("frames_per_thread", "<u4"), ("tap_block", "<u4"), ("channels", "<u4")])
+CONVOLVE_RECORD_DTYPE = np.dtype([("frames_in", "<u8"), ("frames_out", "<u8"), ("frames_written", "<u8"), ("samples_over", "<u8"),
+                                  ("samples_nonfinite", "<u8"), ("out_sample_peak", "<f4"), ("out_sample_peak_db", "<f4"),
+                                  ("state", "<u4"), ("delay_frames", "<u4"), ("max_taps", "<u4"), ("_pad", "<u4")])
+assert C.sizeof(CProgramFir) == 16 and C.sizeof(CProgramConvolveSpec) == 32 and C.sizeof(CProgramConvolveInfo) == 16
+assert C.sizeof(CProgramConvolveRecord) == 64 and CONVOLVE_INFO_DTYPE.itemsize == 16 and CONVOLVE_RECORD_DTYPE.itemsize == 64
+CONVOLVE_MAX_TAPS = 4096
+CONVOLVE_MAX_FIRS = 64
+CONVOLVE_BYPASS = 0xFFFFFFFF
+CONVOLVE_LOWPASS, CONVOLVE_HIGHPASS, CONVOLVE_BANDPASS, CONVOLVE_BANDSTOP = range(4)   # omx_program_convolve_spec.kind
+CONVOLVE_IDLE, CONVOLVE_RUNNING, CONVOLVE_FLUSHED = 0, 1, 2                             # omx_program_convolve_record.state
+
+
+@dataclass
+class ConvolveSpec:
+    """omx_program_convolve_spec: the kind (CONVOLVE_*), the odd tap count, the band edges (LOWPASS uses f_hi_hz, HIGHPASS f_lo_hz,
+    the band kinds both) and Kaiser beta."""
+    kind: int = CONVOLVE_LOWPASS
+    n_taps: int = 255
+    f_lo_hz: float = 0.0
+    f_hi_hz: float = 0.0
+    beta: float = 9.0
+
+    def to_c(self) -> CProgramConvolveSpec:
+        return CProgramConvolveSpec(self.kind, self.n_taps, self.f_lo_hz, self.f_hi_hz, self.beta)
+
+
+def _fir_table(firs, flags: int = 0):
+    """(C array of omx_program_fir, the f32 arrays it points into) of a sequence of tap sequences"""
+    keep = [np.ascontiguousarray(t, np.float32).reshape(-1) for t in firs]
+    table = (CProgramFir * max(len(keep), 1))()
+    for k, t in enumerate(keep):
+        table[k] = CProgramFir(t.ctypes.data if t.size else None, t.size, flags)
+    return table, keep
+
+
+def convolve_plan(api: Api, channels: int, max_taps: int = 1) -> np.ndarray:
+    """The plan of a channel count (omx_program_convolve_plan) as a CONVOLVE_INFO_DTYPE scalar: the main kernel's tile, the frames a
+    thread keeps in registers and the tap block.  Needs no device."""
+    out = np.zeros((1,), CONVOLVE_INFO_DTYPE)
+    api.check(api.fn("program_convolve_plan", C.c_int, [C.c_uint32, C.c_uint32, C.c_void_p])(channels, max_taps, out.ctypes.data))
+    return out[0]
+
+
+def convolve_frames(api: Api, delay_frames: int, frames_in_before: int, frames_out_before: int, frames: int, flush: bool = False) -> int:
+    """Frames a stream emits in a call that brings `frames` frames under delay_frames, after frames_in_before taken and
+    frames_out_before emitted (omx_program_convolve_frames): what d_out has to hold.  Needs no device."""
+    out = C.c_uint64()
+    api.check(api.fn("program_convolve_frames", C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p])(
+        delay_frames, frames_in_before, frames_out_before, frames, 1 if flush else 0, C.byref(out)))
+    return int(out.value)
+
+
+def convolve_check(api: Api, taps, flags: int = 0) -> int:
+    """0 for a FIR the bank takes (omx_program_convolve_check); raises OmxError with status -3 otherwise.  Needs no device."""
+    table, _keep = _fir_table([taps], flags)
+    return api.check(api.fn("program_convolve_check", C.c_int, [C.c_void_p])(C.byref(table[0])))
+
+
+def convolve_design(api: Api, spec: ConvolveSpec, sample_rate: float) -> np.ndarray:
+    """The f32 taps of a spec at a sample rate (omx_program_convolve_design): a Kaiser-windowed linear-phase FIR.  Needs no device."""
+    out, c = np.zeros((max(int(spec.n_taps), 0),), np.float32), spec.to_c()
+    api.check(api.fn("program_convolve_design", C.c_int, [C.c_void_p, C.c_double, C.c_void_p, C.c_uint32])(
+        C.byref(c), sample_rate, out.ctypes.data, out.size))
+    return out
+
+
+def convolve_response(api: Api, taps, sample_rate: float, frequency_hz: float):
+    """(magnitude in dB, phase in radians) of the FIR's H(e^{jw}) (omx_program_convolve_response).  Needs no device."""
+    (table, _keep), mag, ph = _fir_table([taps]), C.c_double(), C.c_double()
+    api.check(api.fn("program_convolve_response", C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p])(
+        C.byref(table[0]), sample_rate, frequency_hz, C.byref(mag), C.byref(ph)))
+    return mag.value, ph.value
+
+
 class ProgramLoudnessBank:
     """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
 
@@ -1568,4 +1665,48 @@ class ProgramLoudnessBank:
         out = np.zeros((1,), MIX_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_mixed", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, bus, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_convolve.h
+    def configure_convolve(self, firs, channels: int, fir_of_channel=None, delay_frames: int = 0):
+        """Set the FIR table (a sequence of f32 tap sequences), the channel count of the PCM the convolve stage takes, which FIR
+        every channel runs (fir_of_channel [n_streams][channels] of table indices or CONVOLVE_BYPASS, None: FIR 0 everywhere) and
+        the compensated delay D in frames, at most the longest referenced FIR's taps minus one; (T - 1) / 2 leaves a symmetric FIR's
+        output in place.  Only while no stream of the stage holds frames: a new bank, or after reset_convolve() of every stream."""
+        table, _keep = _fir_table(firs)
+        foc = None
+        if fir_of_channel is not None:
+            foc = np.ascontiguousarray(fir_of_channel, np.uint32).reshape(-1)
+            if foc.size != self.n_streams * channels:
+                raise ValueError(f"fir_of_channel: {foc.size} entries for {self.n_streams} streams of {channels} channels")
+        self.api.check(self.api.fn("program_loudness_bank_convolve_configure", C.c_int,
+                                   [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32])(
+            self._h, channels, table if len(firs) else None, len(firs), foc.ctypes.data if foc is not None else None, delay_frames))
+
+    def reset_convolve(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the convolve stage forget their frames and are idle again (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_convolve_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def convolve(self, d_in: int, frames_capacity: int, d_out: int, out_capacity: int, frames: Optional[Sequence[int]] = None,
+                 flush_mask: Optional[Sequence[int]] = None, stream: int = 0) -> int:
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels]) and write the output frames they complete to
+        d_out[s][0 ..) (f32 [n_streams][out_capacity][channels]); with the stream flagged in flush_mask, the tail as well (the input
+        continued with zeros).  convolve_frames() says how many frames a call emits.  Out of place.  Returns the device pointer to
+        omx_program_convolve_record[n_streams] (CONVOLVE_RECORD_DTYPE); `frames_written` says how many frames each stream got."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        fl = self._per_stream(flush_mask, np.uint8, "flush_mask")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_convolve", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None, C.c_void_p(d_out or 0),
+                         out_capacity, fl.ctypes.data if fl is not None else None, C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_convolved(self, stream_index: int) -> np.ndarray:
+        """One stream's convolve record as a CONVOLVE_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), CONVOLVE_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_convolved", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
         return out[0]
