@@ -57,6 +57,12 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_convolve.h)
     CONVOLVE_LOWPASS, CONVOLVE_MAX_FIRS, CONVOLVE_MAX_TAPS, CONVOLVE_RECORD_DTYPE, CONVOLVE_RUNNING, ConvolveSpec, CProgramConvolveInfo,
     CProgramConvolveRecord, CProgramConvolveSpec, CProgramFir, convolve_check, convolve_design, convolve_frames, convolve_plan,
     convolve_response)
+from .program_loudness import (  # noqa: F401  (include/omx/program_dynamics.h)
+    DYNAMICS_BYPASS, DYNAMICS_CURVE_POINTS, DYNAMICS_FLUSHED, DYNAMICS_IDLE, DYNAMICS_INFO_DTYPE, DYNAMICS_L_MAX, DYNAMICS_L_MIN,
+    DYNAMICS_MAX_ATTACK, DYNAMICS_MAX_CURVES, DYNAMICS_MAX_GAIN, DYNAMICS_MAX_HOLD, DYNAMICS_MAX_POINTS, DYNAMICS_MAX_STEP,
+    DYNAMICS_OCTAVE_DB, DYNAMICS_RECORD_DTYPE, DYNAMICS_RUNNING, DYNAMICS_TABLE_ENTRIES, CProgramDynamicsCurve, CProgramDynamicsInfo,
+    CProgramDynamicsPoint, CProgramDynamicsRecord, CProgramDynamicsSpec, DynamicsCurve, DynamicsSpec, dynamics_check, dynamics_design,
+    dynamics_frames, dynamics_from_points, dynamics_gain_db, dynamics_latency, dynamics_plan, dynamics_tables, dynamics_time)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

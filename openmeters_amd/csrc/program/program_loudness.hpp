@@ -20,6 +20,7 @@
 #include "program_filter.hpp"
 #include "program_mix.hpp"
 #include "program_convolve.hpp"
+#include "program_dynamics.hpp"
 
 namespace omx {
 
@@ -199,6 +200,12 @@ public:
     int convolve(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, float* d_out, uint64_t out_capacity,
                  const uint8_t* flush_mask, hipStream_t stream, const omx_program_convolve_record** d_convolved);
     int fetch_convolved(uint64_t stream_index, omx_program_convolve_record* dst);
+    // include/omx/program_dynamics.h (program_dynamics.cpp)
+    int dynamics_configure(uint32_t channels, const omx_program_dynamics_curve* curves, uint32_t n_curves, const uint32_t* curve_of_stream);
+    int dynamics_reset(const uint8_t* reset_mask);
+    int dynamics(const float* d_in, const float* d_key, uint64_t frames_capacity, const uint32_t* frames, float* d_out, float* d_gain_db,
+                 uint64_t out_capacity, const uint8_t* flush_mask, hipStream_t stream, const omx_program_dynamics_record** d_records);
+    int fetch_dynamics(uint64_t stream_index, omx_program_dynamics_record* dst);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -313,6 +320,9 @@ private:
     // convolve: nothing is allocated or launched until convolve_configure
     CvArgs convolve_args() const;
     std::unique_ptr<ProgramConvolve> convolve_;
+    // dynamics: nothing is allocated or launched until dynamics_configure
+    DyArgs dynamics_args() const;
+    std::unique_ptr<ProgramDynamics> dynamics_;
 };
 
 }  // namespace omx

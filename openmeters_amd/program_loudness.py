@@ -1015,6 +1015,172 @@ def convolve_response(api: Api, taps, sample_rate: float, frequency_hz: float):
     return mag.value, ph.value
 
 
+class CProgramDynamicsCurve(C.Structure):
+    """omx_program_dynamics_curve (include/omx/program_dynamics.h)"""
+    _fields_ = [("T", C.c_int32 * 769), ("detector_mask", C.c_uint32), ("attack_frames", C.c_uint32), ("hold_frames", C.c_uint32),
+                ("release_step", C.c_int64)]
+
+
+class CProgramDynamicsSpec(C.Structure):
+    """omx_program_dynamics_spec (include/omx/program_dynamics.h)"""
+    _fields_ = [("threshold_db", C.c_double), ("ratio", C.c_double), ("knee_db", C.c_double), ("expander_threshold_db", C.c_double),
+                ("expander_ratio", C.c_double), ("range_db", C.c_double), ("makeup_db", C.c_double)]
+
+
+class CProgramDynamicsPoint(C.Structure):
+    """omx_program_dynamics_point (include/omx/program_dynamics.h)"""
+    _fields_ = [("in_db", C.c_double), ("out_db", C.c_double)]
+
+
+class CProgramDynamicsInfo(C.Structure):
+    """omx_program_dynamics_info (include/omx/program_dynamics.h)"""
+    _fields_ = [("level_tile", C.c_uint32), ("hold_tile", C.c_uint32), ("hold_max_window", C.c_uint32), ("release_tile", C.c_uint32),
+                ("smooth_tile", C.c_uint32), ("chain_threads", C.c_uint32), ("channels", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CProgramDynamicsRecord(C.Structure):
+    """omx_program_dynamics_record (include/omx/program_dynamics.h)"""
+    _fields_ = [("frames_in", C.c_uint64), ("frames_out", C.c_uint64), ("frames_written", C.c_uint64), ("frames_reduced", C.c_uint64),
+                ("frames_boosted", C.c_uint64), ("samples_over", C.c_uint64), ("samples_nonfinite", C.c_uint64), ("min_gain", C.c_int64),
+                ("max_gain", C.c_int64), ("min_gain_db", C.c_float), ("max_gain_db", C.c_float), ("out_sample_peak", C.c_float),
+                ("out_sample_peak_db", C.c_float), ("state", C.c_uint32), ("latency_frames", C.c_uint32), ("curve_index", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+DYNAMICS_INFO_DTYPE = np.dtype([("level_tile", "<u4"), ("hold_tile", "<u4"), ("hold_max_window", "<u4"), ("release_tile", "<u4"),
+                                ("smooth_tile", "<u4"), ("chain_threads", "<u4"), ("channels", "<u4"), ("_pad", "<u4")])
+DYNAMICS_RECORD_DTYPE = np.dtype([("frames_in", "<u8"), ("frames_out", "<u8"), ("frames_written", "<u8"), ("frames_reduced", "<u8"),
+                                  ("frames_boosted", "<u8"), ("samples_over", "<u8"), ("samples_nonfinite", "<u8"), ("min_gain", "<i8"),
+                                  ("max_gain", "<i8"), ("min_gain_db", "<f4"), ("max_gain_db", "<f4"), ("out_sample_peak", "<f4"),
+                                  ("out_sample_peak_db", "<f4"), ("state", "<u4"), ("latency_frames", "<u4"), ("curve_index", "<u4"),
+                                  ("_pad", "<u4")])
+assert C.sizeof(CProgramDynamicsCurve) == 3096 and C.sizeof(CProgramDynamicsSpec) == 56 and C.sizeof(CProgramDynamicsPoint) == 16
+assert C.sizeof(CProgramDynamicsInfo) == 32 and C.sizeof(CProgramDynamicsRecord) == 104
+assert DYNAMICS_INFO_DTYPE.itemsize == 32 and DYNAMICS_RECORD_DTYPE.itemsize == 104
+DYNAMICS_CURVE_POINTS = 769
+DYNAMICS_TABLE_ENTRIES = 257
+DYNAMICS_MAX_CURVES = 64
+DYNAMICS_MAX_POINTS = 16
+DYNAMICS_MAX_ATTACK = 4096
+DYNAMICS_MAX_HOLD = 16384
+DYNAMICS_L_MIN, DYNAMICS_L_MAX = -40 * 65536, 8 * 65536
+DYNAMICS_MAX_GAIN = 40 * 65536
+DYNAMICS_MAX_STEP = 40 << 32
+DYNAMICS_OCTAVE_DB = 6.020599913279624
+DYNAMICS_BYPASS = 0xFFFFFFFF
+DYNAMICS_IDLE, DYNAMICS_RUNNING, DYNAMICS_FLUSHED = 0, 1, 2                             # omx_program_dynamics_record.state
+
+
+@dataclass
+class DynamicsSpec:
+    """omx_program_dynamics_spec: a compressor (threshold, ratio, soft knee), an optional downward expander below it (its threshold,
+    ratio and largest reduction) and the make-up gain, all in dB."""
+    threshold_db: float = -20.0
+    ratio: float = 4.0
+    knee_db: float = 0.0
+    expander_threshold_db: float = -60.0
+    expander_ratio: float = 1.0
+    range_db: float = float("inf")
+    makeup_db: float = 0.0
+
+    def to_c(self) -> CProgramDynamicsSpec:
+        return CProgramDynamicsSpec(self.threshold_db, self.ratio, self.knee_db, self.expander_threshold_db, self.expander_ratio,
+                                    self.range_db, self.makeup_db)
+
+
+@dataclass
+class DynamicsCurve:
+    """omx_program_dynamics_curve: the table T[769] (gain in 2^-16 octave at level L_MIN + 4096 k), the channels the level is taken
+    from, the attack and hold in frames and the release step in 2^-32 octave per frame."""
+    T: Sequence[int]
+    detector_mask: int = 1
+    attack_frames: int = 1
+    hold_frames: int = 0
+    release_step: int = DYNAMICS_MAX_STEP
+
+    def to_c(self) -> CProgramDynamicsCurve:
+        c = CProgramDynamicsCurve()
+        t = np.ascontiguousarray(self.T, np.int32).reshape(-1)
+        if t.size != DYNAMICS_CURVE_POINTS:
+            raise ValueError(f"a dynamics curve has {DYNAMICS_CURVE_POINTS} entries, not {t.size}")
+        C.memmove(c.T, t.ctypes.data, t.nbytes)
+        c.detector_mask, c.attack_frames, c.hold_frames, c.release_step = self.detector_mask, self.attack_frames, self.hold_frames, self.release_step
+        return c
+
+
+def _dynamics_c(curve) -> CProgramDynamicsCurve:
+    return curve if isinstance(curve, CProgramDynamicsCurve) else curve.to_c()
+
+
+def dynamics_plan(api: Api, channels: int) -> np.ndarray:
+    """The tiles of the dynamics passes (omx_program_dynamics_plan) as a DYNAMICS_INFO_DTYPE scalar.  Needs no device."""
+    out = np.zeros((1,), DYNAMICS_INFO_DTYPE)
+    api.check(api.fn("program_dynamics_plan", C.c_int, [C.c_uint32, C.c_void_p])(channels, out.ctypes.data))
+    return out[0]
+
+
+def dynamics_tables(api: Api):
+    """(LOG int32 [257], EXP uint64 [257]) as the library holds them (omx_program_dynamics_tables).  Needs no device."""
+    lg, ex = np.zeros((DYNAMICS_TABLE_ENTRIES,), np.int32), np.zeros((DYNAMICS_TABLE_ENTRIES,), np.uint64)
+    api.check(api.fn("program_dynamics_tables", C.c_int, [C.c_void_p, C.c_void_p])(lg.ctypes.data, ex.ctypes.data))
+    return lg, ex
+
+
+def dynamics_check(api: Api, curve) -> int:
+    """0 for a curve the bank takes (omx_program_dynamics_check); raises OmxError with status -3 otherwise.  Needs no device."""
+    c = _dynamics_c(curve)
+    return api.check(api.fn("program_dynamics_check", C.c_int, [C.c_void_p])(C.byref(c)))
+
+
+def dynamics_latency(api: Api, curve) -> int:
+    """The latency in frames of a stream on the curve, attack_frames - 1 (omx_program_dynamics_latency).  Needs no device."""
+    c, out = _dynamics_c(curve), C.c_uint32()
+    api.check(api.fn("program_dynamics_latency", C.c_int, [C.c_void_p, C.c_void_p])(C.byref(c), C.byref(out)))
+    return int(out.value)
+
+
+def dynamics_design(api: Api, spec: DynamicsSpec) -> np.ndarray:
+    """The table int32 [769] of a spec (omx_program_dynamics_design).  Needs no device."""
+    c, s = CProgramDynamicsCurve(), spec.to_c()
+    api.check(api.fn("program_dynamics_design", C.c_int, [C.c_void_p, C.c_void_p])(C.byref(s), C.byref(c)))
+    return np.array(c.T, np.int32)
+
+
+def dynamics_from_points(api: Api, points) -> np.ndarray:
+    """The table int32 [769] of up to 16 (in_db, out_db) pairs, piecewise linear in dB with slope 1 outside them: the transfer
+    function of sox compand (omx_program_dynamics_from_points).  Needs no device."""
+    pts = list(points)
+    arr, c = (CProgramDynamicsPoint * max(len(pts), 1))(), CProgramDynamicsCurve()
+    for k, (a, b) in enumerate(pts):
+        arr[k] = CProgramDynamicsPoint(a, b)
+    api.check(api.fn("program_dynamics_from_points", C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p])(arr, len(pts), C.byref(c)))
+    return np.array(c.T, np.int32)
+
+
+def dynamics_gain_db(api: Api, T, level_db: float) -> float:
+    """The table's gain in dB at a level in dB, evaluated as the kernel evaluates it (omx_program_dynamics_gain_db).  Needs no device."""
+    c, out = DynamicsCurve(T).to_c(), C.c_double()
+    api.check(api.fn("program_dynamics_gain_db", C.c_int, [C.c_void_p, C.c_double, C.c_void_p])(C.byref(c), level_db, C.byref(out)))
+    return out.value
+
+
+def dynamics_time(api: Api, sample_rate: float, attack_ms: float, hold_ms: float, release_db_per_s: float):
+    """(attack_frames, hold_frames, release_step) of times at a sample rate (omx_program_dynamics_time).  Needs no device."""
+    a, h, d = C.c_uint32(), C.c_uint32(), C.c_int64()
+    api.check(api.fn("program_dynamics_time", C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p])(
+        sample_rate, attack_ms, hold_ms, release_db_per_s, C.byref(a), C.byref(h), C.byref(d)))
+    return int(a.value), int(h.value), int(d.value)
+
+
+def dynamics_frames(api: Api, latency_frames: int, frames_in_before: int, frames_out_before: int, frames: int, flush: bool = False) -> int:
+    """Frames a stream emits in a call that brings `frames` frames under a latency, after frames_in_before taken and
+    frames_out_before emitted (omx_program_dynamics_frames): what d_out has to hold.  Needs no device."""
+    out = C.c_uint64()
+    api.check(api.fn("program_dynamics_frames", C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p])(
+        latency_frames, frames_in_before, frames_out_before, frames, 1 if flush else 0, C.byref(out)))
+    return int(out.value)
+
+
 class ProgramLoudnessBank:
     """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
 
@@ -1708,5 +1874,52 @@ class ProgramLoudnessBank:
         """One stream's convolve record as a CONVOLVE_RECORD_DTYPE scalar; synchronises."""
         out = np.zeros((1,), CONVOLVE_RECORD_DTYPE)
         self.api.check(self.api.fn("program_loudness_bank_fetch_convolved", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
+            self._h, stream_index, out.ctypes.data))
+        return out[0]
+
+    # ---- include/omx/program_dynamics.h
+    def configure_dynamics(self, curves, channels: int, curve_of_stream: Optional[Sequence[int]] = None):
+        """Set the curve table (a sequence of DynamicsCurve), the channel count of the PCM the dynamics stage takes and which curve
+        every stream runs (table indices or DYNAMICS_BYPASS, None: curve 0 everywhere).  A stream's latency is its curve's
+        attack_frames - 1; a bypassed stream is delayed by the largest latency of the table.  Only while no stream of the stage
+        holds frames: a new bank, or after reset_dynamics() of every stream."""
+        curves = list(curves)
+        table = (CProgramDynamicsCurve * max(len(curves), 1))()
+        for k, c in enumerate(curves):
+            table[k] = _dynamics_c(c)
+        cos = self._per_stream(curve_of_stream, np.uint32, "curve_of_stream")
+        self.api.check(self.api.fn("program_loudness_bank_dynamics_configure", C.c_int,
+                                   [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])(
+            self._h, channels, table if curves else None, len(curves), cos.ctypes.data if cos is not None else None))
+
+    def reset_dynamics(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the dynamics stage forget their frames and their history and are idle again (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_dynamics_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def dynamics(self, d_in: int, frames_capacity: int, d_out: int, out_capacity: int, frames: Optional[Sequence[int]] = None,
+                 flush_mask: Optional[Sequence[int]] = None, d_key: int = 0, d_gain_db: int = 0, stream: int = 0) -> int:
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels]), with the level taken from d_key (same layout;
+        0: from d_in), and write the frames they complete, under the gain of each stream's curve, to d_out[s][0 ..) (f32 [n_streams]
+        [out_capacity][channels]) and their gains in dB to d_gain_db[s][0 ..) (f32 [n_streams][out_capacity]; 0: no trace); with the
+        stream flagged in flush_mask, the held frames as well.  dynamics_frames() says how many frames a call emits.  Out of place.
+        Returns the device pointer to omx_program_dynamics_record[n_streams] (DYNAMICS_RECORD_DTYPE); `frames_written` says how many
+        frames each stream got."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        fl = self._per_stream(flush_mask, np.uint8, "flush_mask")
+        out = C.c_void_p()
+        f = self.api.fn("program_loudness_bank_dynamics", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                         C.c_void_p, C.POINTER(C.c_void_p)])
+        self.api.check(f(self._h, C.c_void_p(d_in or 0), C.c_void_p(d_key or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                         C.c_void_p(d_out or 0), C.c_void_p(d_gain_db or 0), out_capacity, fl.ctypes.data if fl is not None else None,
+                         C.c_void_p(stream or 0), C.byref(out)))
+        return out.value or 0
+
+    def fetch_dynamics(self, stream_index: int) -> np.ndarray:
+        """One stream's dynamics record as a DYNAMICS_RECORD_DTYPE scalar; synchronises."""
+        out = np.zeros((1,), DYNAMICS_RECORD_DTYPE)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_dynamics", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
