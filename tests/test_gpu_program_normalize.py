@@ -227,11 +227,16 @@ def test_apply_is_exact_on_a_row_of_many_tiles(torch_dev, omx, in_place):
     apply_case(torch_dev, omx, xs, nr.LONG_FRAMES, nr.LONG_CHANNELS, [1.3, 1.2, 0.7], in_place, ("long", in_place))
 
 
-@pytest.mark.parametrize("in_offset,out_offset", [(1, 0), (0, 1), (3, 2), (2, 2)])
-def test_apply_is_exact_when_loads_and_stores_are_aligned_differently(torch_dev, omx, in_offset, out_offset):
-    """d_in one float off a 16-byte boundary against an aligned d_out (the dword-load form), and the other combinations"""
-    xs = [nr.planted(nr.noise(80 + s, f, 2), 80 + s) for s, f in enumerate((1000, 999, 517, 3, 0, 2100))]
-    apply_case(torch_dev, omx, xs, 2100, 2, [1.7, 0.3, 1.0, 2.5, 4.0, 1.05], False, ("offsets", in_offset, out_offset), in_offset, out_offset)
+OFFSET_CASES = [(ch, a_in, a_out) for ch in (2, 3, 8) for a_in in range(4) for a_out in range(4)]      # (2 channels keep their earlier ids)
+
+
+@pytest.mark.parametrize("ch,in_offset,out_offset", OFFSET_CASES,
+                         ids=[f"{a_in}-{a_out}" if ch == 2 else f"{a_in}-{a_out}-{ch}ch" for ch, a_in, a_out in OFFSET_CASES])
+def test_apply_is_exact_when_loads_and_stores_are_aligned_differently(torch_dev, omx, ch, in_offset, out_offset):
+    """d_in one float off a 16-byte boundary against an aligned d_out (the dword-load form), and every other pair of offsets; at 8
+    channels a row leaves its boundary through the offset alone"""
+    xs = [nr.planted(nr.noise(80 + s, f, ch), 80 + s) for s, f in enumerate((1000, 999, 517, 3, 0, 2100))]
+    apply_case(torch_dev, omx, xs, 2100, ch, [1.7, 0.3, 1.0, 2.5, 4.0, 1.05], False, ("offsets", ch, in_offset, out_offset), in_offset, out_offset)
 
 
 # ---------------------------------------------------------------- 4. gain routing
