@@ -63,6 +63,12 @@ from .program_loudness import (  # noqa: F401  (include/omx/program_dynamics.h)
     DYNAMICS_OCTAVE_DB, DYNAMICS_RECORD_DTYPE, DYNAMICS_RUNNING, DYNAMICS_TABLE_ENTRIES, CProgramDynamicsCurve, CProgramDynamicsInfo,
     CProgramDynamicsPoint, CProgramDynamicsRecord, CProgramDynamicsSpec, DynamicsCurve, DynamicsSpec, dynamics_check, dynamics_design,
     dynamics_frames, dynamics_from_points, dynamics_gain_db, dynamics_latency, dynamics_plan, dynamics_tables, dynamics_time)
+from .program_loudness import (  # noqa: F401  (include/omx/program_spectrum.h)
+    SPECTRUM_BANDLIMITED, SPECTRUM_DB_FLOOR, SPECTRUM_INFO_DTYPE, SPECTRUM_MAX_BANDS, SPECTRUM_MAX_PROBES, SPECTRUM_MAX_TAPS,
+    SPECTRUM_RECORD_DTYPE, SPECTRUM_RUN, SPECTRUM_SUMMARY_DTYPE, SPECTRUM_TONE, CProgramSpectrumInfo, CProgramSpectrumMatchSpec,
+    CProgramSpectrumQc, CProgramSpectrumRecord, CProgramSpectrumRule, CProgramSpectrumSummary, SpectrumMatchSpec, SpectrumQc, SpectrumRule,
+    spectrum_bands, spectrum_density, spectrum_match, spectrum_match_spec_default, spectrum_plan, spectrum_qc_default,
+    spectrum_rule_default, spectrum_summarize, spectrum_transforms, spectrum_window)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OMX_HIP_LIB") or os.path.join(_HERE, "csrc", "libomx_hip.so")  # OMX_HIP_LIB: A/B builds (tuning)

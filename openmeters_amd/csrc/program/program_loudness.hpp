@@ -21,6 +21,7 @@
 #include "program_mix.hpp"
 #include "program_convolve.hpp"
 #include "program_dynamics.hpp"
+#include "program_spectrum.hpp"
 
 namespace omx {
 
@@ -206,6 +207,12 @@ public:
     int dynamics(const float* d_in, const float* d_key, uint64_t frames_capacity, const uint32_t* frames, float* d_out, float* d_gain_db,
                  uint64_t out_capacity, const uint8_t* flush_mask, hipStream_t stream, const omx_program_dynamics_record** d_records);
     int fetch_dynamics(uint64_t stream_index, omx_program_dynamics_record* dst);
+    // include/omx/program_spectrum.h (program_spectrum.cpp)
+    int spectrum_configure(const omx_program_spectrum_rule* rule, uint32_t channels);
+    int spectrum_reset(const uint8_t* reset_mask);
+    int spectrum(const float* d_in, uint64_t frames_capacity, const uint32_t* frames, const uint8_t* finish_mask, hipStream_t stream,
+                 const omx_program_spectrum_record** d_records, const double** d_sums);
+    int fetch_spectrum(uint64_t stream_index, omx_program_spectrum_record* record, double* sums);
     void form(int f) { form_ = f; }
     int last_form() const { return last_form_; }
 
@@ -323,6 +330,9 @@ private:
     // dynamics: nothing is allocated or launched until dynamics_configure
     DyArgs dynamics_args() const;
     std::unique_ptr<ProgramDynamics> dynamics_;
+    // spectrum: nothing is allocated or launched until spectrum_configure
+    SpArgs spectrum_args() const;
+    std::unique_ptr<ProgramSpectrum> spectrum_;
 };
 
 }  // namespace omx

@@ -1181,6 +1181,198 @@ def dynamics_frames(api: Api, latency_frames: int, frames_in_before: int, frames
     return int(out.value)
 
 
+# ---- include/omx/program_spectrum.h
+class CProgramSpectrumRule(C.Structure):
+    """omx_program_spectrum_rule (include/omx/program_spectrum.h)"""
+    _fields_ = [("fft_size", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CProgramSpectrumInfo(C.Structure):
+    """omx_program_spectrum_info (include/omx/program_spectrum.h)"""
+    _fields_ = [("fft_size", C.c_uint32), ("hop", C.c_uint32), ("bins", C.c_uint32), ("threads", C.c_uint32),
+                ("transforms_per_workgroup", C.c_uint32), ("run", C.c_uint32), ("lds_bytes", C.c_uint32), ("channels", C.c_uint32),
+                ("scratch_bytes", C.c_uint64), ("state_bytes", C.c_uint64)]
+
+
+class CProgramSpectrumRecord(C.Structure):
+    """omx_program_spectrum_record (include/omx/program_spectrum.h)"""
+    _fields_ = [("frames", C.c_uint64), ("transforms", C.c_uint64 * 8), ("skipped", C.c_uint64 * 8), ("fft_size", C.c_uint32),
+                ("channels", C.c_uint32), ("finished", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+SPECTRUM_MAX_PROBES = 8
+
+
+class CProgramSpectrumQc(C.Structure):
+    """omx_program_spectrum_qc (include/omx/program_spectrum.h)"""
+    _fields_ = [("occupied_fraction", C.c_double), ("bandwidth_min_ratio", C.c_double), ("tone_db", C.c_double),
+                ("probe_hz", C.c_double * SPECTRUM_MAX_PROBES), ("n_probes", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class CProgramSpectrumSummary(C.Structure):
+    """omx_program_spectrum_summary (include/omx/program_spectrum.h)"""
+    _fields_ = [("verdict", C.c_uint32), ("n_probes", C.c_uint32), ("total_db", C.c_double), ("peak_hz", C.c_double),
+                ("peak_db", C.c_double), ("occupied_hz", C.c_double), ("prominence_db", C.c_double * SPECTRUM_MAX_PROBES)]
+
+
+class CProgramSpectrumMatchSpec(C.Structure):
+    """omx_program_spectrum_match_spec (include/omx/program_spectrum.h)"""
+    _fields_ = [("max_boost_db", C.c_double), ("max_cut_db", C.c_double), ("low_hz", C.c_double), ("high_hz", C.c_double),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+SPECTRUM_INFO_DTYPE = np.dtype([("fft_size", "<u4"), ("hop", "<u4"), ("bins", "<u4"), ("threads", "<u4"),
+                                ("transforms_per_workgroup", "<u4"), ("run", "<u4"), ("lds_bytes", "<u4"), ("channels", "<u4"),
+                                ("scratch_bytes", "<u8"), ("state_bytes", "<u8")])
+SPECTRUM_RECORD_DTYPE = np.dtype([("frames", "<u8"), ("transforms", "<u8", (8,)), ("skipped", "<u8", (8,)), ("fft_size", "<u4"),
+                                  ("channels", "<u4"), ("finished", "<u4"), ("_pad", "<u4")])
+SPECTRUM_SUMMARY_DTYPE = np.dtype([("verdict", "<u4"), ("n_probes", "<u4"), ("total_db", "<f8"), ("peak_hz", "<f8"), ("peak_db", "<f8"),
+                                   ("occupied_hz", "<f8"), ("prominence_db", "<f8", (SPECTRUM_MAX_PROBES,))])
+assert C.sizeof(CProgramSpectrumRule) == 8 and C.sizeof(CProgramSpectrumInfo) == 48 and C.sizeof(CProgramSpectrumRecord) == 152
+assert C.sizeof(CProgramSpectrumQc) == 96 and C.sizeof(CProgramSpectrumSummary) == 104 and C.sizeof(CProgramSpectrumMatchSpec) == 40
+assert SPECTRUM_INFO_DTYPE.itemsize == 48 and SPECTRUM_RECORD_DTYPE.itemsize == 152 and SPECTRUM_SUMMARY_DTYPE.itemsize == 104
+SPECTRUM_RUN, SPECTRUM_MAX_BANDS, SPECTRUM_MAX_TAPS, SPECTRUM_DB_FLOOR = 16, 48, 4095, -400.0
+SPECTRUM_BANDLIMITED, SPECTRUM_TONE = 1, 2      # omx_program_spectrum_summary.verdict
+
+
+@dataclass
+class SpectrumRule:
+    """omx_program_spectrum_rule: Welch's method with a periodic Hann of fft_size points (2048, 4096 or 8192) at half overlap."""
+    fft_size: int = 4096
+    flags: int = 0
+
+    def to_c(self) -> CProgramSpectrumRule:
+        return CProgramSpectrumRule(self.fft_size, self.flags)
+
+
+@dataclass
+class SpectrumQc:
+    """omx_program_spectrum_qc: the fraction of the power the occupied bandwidth holds, the share of fs/2 below which a programme
+    counts as band-limited, the prominence in dB at which a probe counts as a tone, the probe frequencies."""
+    occupied_fraction: float = 0.9999
+    bandwidth_min_ratio: float = 0.8
+    tone_db: float = 20.0
+    probe_hz: Sequence[float] = (50.0, 100.0, 150.0, 60.0, 120.0, 180.0)
+    flags: int = 0
+    n_probes: Optional[int] = None      # None: len(probe_hz)
+
+    def to_c(self) -> CProgramSpectrumQc:
+        probes = list(self.probe_hz)[:SPECTRUM_MAX_PROBES]
+        n = len(self.probe_hz) if self.n_probes is None else self.n_probes
+        return CProgramSpectrumQc(self.occupied_fraction, self.bandwidth_min_ratio, self.tone_db,
+                                  (C.c_double * SPECTRUM_MAX_PROBES)(*probes), n, self.flags)
+
+
+@dataclass
+class SpectrumMatchSpec:
+    """omx_program_spectrum_match_spec: the most a match FIR boosts and cuts, and the band outside which its gain is held."""
+    max_boost_db: float = 12.0
+    max_cut_db: float = 12.0
+    low_hz: float = 40.0
+    high_hz: float = 0.45 * 48000.0
+    flags: int = 0
+
+    def to_c(self) -> CProgramSpectrumMatchSpec:
+        return CProgramSpectrumMatchSpec(self.max_boost_db, self.max_cut_db, self.low_hz, self.high_hz, self.flags, 0)
+
+
+def _density_arg(density, fft_size: int) -> np.ndarray:
+    d = np.ascontiguousarray(density, np.float64).reshape(-1)
+    if fft_size in (2048, 4096, 8192) and d.size != fft_size // 2 + 1:
+        raise ValueError(f"density: {d.size} entries for {fft_size // 2 + 1} bins")
+    return d
+
+
+def spectrum_rule_default(api: Api) -> SpectrumRule:
+    """The header's default rule as the library fills it (omx_program_spectrum_rule_default).  Needs no device."""
+    c = CProgramSpectrumRule()
+    api.check(api.fn("program_spectrum_rule_default", C.c_int, [C.c_void_p])(C.byref(c)))
+    return SpectrumRule(c.fft_size, c.flags)
+
+
+def spectrum_qc_default(api: Api) -> SpectrumQc:
+    """The header's default QC rule (omx_program_spectrum_qc_default).  Needs no device."""
+    c = CProgramSpectrumQc()
+    api.check(api.fn("program_spectrum_qc_default", C.c_int, [C.c_void_p])(C.byref(c)))
+    return SpectrumQc(c.occupied_fraction, c.bandwidth_min_ratio, c.tone_db, tuple(c.probe_hz[:c.n_probes]), c.flags)
+
+
+def spectrum_match_spec_default(api: Api, sample_rate: float) -> SpectrumMatchSpec:
+    """The header's default match spec at a sample rate (omx_program_spectrum_match_spec_default).  Needs no device."""
+    c = CProgramSpectrumMatchSpec()
+    api.check(api.fn("program_spectrum_match_spec_default", C.c_int, [C.c_double, C.c_void_p])(sample_rate, C.byref(c)))
+    return SpectrumMatchSpec(c.max_boost_db, c.max_cut_db, c.low_hz, c.high_hz, c.flags)
+
+
+def spectrum_plan(api: Api, rule: SpectrumRule, channels: int, n_streams: int = 1, frames: int = 0) -> np.ndarray:
+    """The transform kernel's tile and the memory of a bank (omx_program_spectrum_plan) as a SPECTRUM_INFO_DTYPE scalar.  Needs no
+    device."""
+    out, c = np.zeros((1,), SPECTRUM_INFO_DTYPE), rule.to_c()
+    api.check(api.fn("program_spectrum_plan", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p])(
+        C.byref(c), channels, n_streams, frames, out.ctypes.data))
+    return out[0]
+
+
+def spectrum_window(api: Api, fft_size: int) -> np.ndarray:
+    """The window of a transform size as the kernels take it, f32 [fft_size] (omx_program_spectrum_window).  Needs no device."""
+    out = np.zeros((max(int(fft_size), 1),), np.float32)
+    api.check(api.fn("program_spectrum_window", C.c_int, [C.c_uint32, C.c_void_p])(fft_size, out.ctypes.data))
+    return out
+
+
+def spectrum_transforms(api: Api, frames: int, finished: bool, fft_size: int) -> int:
+    """Transforms a stream of `frames` frames has taken (omx_program_spectrum_transforms).  Needs no device."""
+    out = C.c_uint64()
+    api.check(api.fn("program_spectrum_transforms", C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p])(
+        frames, 1 if finished else 0, fft_size, C.byref(out)))
+    return int(out.value)
+
+
+def spectrum_density(api: Api, record: np.ndarray, sums: np.ndarray, channel: int) -> np.ndarray:
+    """The one-sided mean square per bin of one channel, f64 [fft_size / 2 + 1], from a SPECTRUM_RECORD_DTYPE record and its sums
+    [channels][bins] (omx_program_spectrum_density).  Needs no device."""
+    rec = np.ascontiguousarray(np.asarray(record, SPECTRUM_RECORD_DTYPE).reshape(1))
+    s = np.ascontiguousarray(sums, np.float64)
+    bins = int(rec["fft_size"][0]) // 2 + 1
+    if s.size != int(rec["channels"][0]) * bins:
+        raise ValueError(f"sums: {s.size} entries for {int(rec['channels'][0])} channels of {bins} bins")
+    out = np.zeros((bins,), np.float64)
+    api.check(api.fn("program_spectrum_density", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p])(
+        rec.ctypes.data, s.ctypes.data, channel, out.ctypes.data))
+    return out
+
+
+def spectrum_bands(api: Api, density, fft_size: int, sample_rate: float, fraction: int = 3):
+    """(centre_hz, level_db) of the octave (fraction 1) or third-octave (3) bands of IEC 61260-1 that lie inside the spectrum
+    (omx_program_spectrum_bands); a full-scale sine reads 0 dB.  Needs no device."""
+    d = _density_arg(density, fft_size)
+    centre, level, n = np.zeros((SPECTRUM_MAX_BANDS,)), np.zeros((SPECTRUM_MAX_BANDS,)), C.c_uint32(SPECTRUM_MAX_BANDS)
+    api.check(api.fn("program_spectrum_bands", C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])(
+        d.ctypes.data, fft_size, sample_rate, fraction, centre.ctypes.data, level.ctypes.data, C.byref(n)))
+    return centre[:n.value].copy(), level[:n.value].copy()
+
+
+def spectrum_summarize(api: Api, qc: SpectrumQc, density, fft_size: int, sample_rate: float) -> np.ndarray:
+    """The QC figures of one density as a SPECTRUM_SUMMARY_DTYPE scalar: total level, peak, occupied bandwidth, the prominence of
+    every probe and the verdict bits (omx_program_spectrum_summarize).  Needs no device."""
+    d, c, out = _density_arg(density, fft_size), qc.to_c(), np.zeros((1,), SPECTRUM_SUMMARY_DTYPE)
+    api.check(api.fn("program_spectrum_summarize", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p])(
+        C.byref(c), d.ctypes.data, fft_size, sample_rate, out.ctypes.data))
+    return out[0]
+
+
+def spectrum_match(api: Api, density_source, density_target, fft_size: int, sample_rate: float, spec: SpectrumMatchSpec,
+                   n_taps: int) -> np.ndarray:
+    """The taps, f32 [n_taps], of a linear-phase FIR for the convolve stage that brings the source's tonal balance to the target's
+    (omx_program_spectrum_match).  Needs no device."""
+    ds, dt, c = _density_arg(density_source, fft_size), _density_arg(density_target, fft_size), spec.to_c()
+    out = np.zeros((max(int(n_taps), 1),), np.float32)
+    api.check(api.fn("program_spectrum_match", C.c_int,
+                     [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_uint32])(
+        ds.ctypes.data, dt.ctypes.data, fft_size, sample_rate, C.byref(c), out.ctypes.data, n_taps))
+    return out[:n_taps]
+
+
 class ProgramLoudnessBank:
     """S programme meters.  `process` takes device PCM f32 [n_streams][frames_capacity][channels], any frame count per stream."""
 
@@ -1923,3 +2115,43 @@ class ProgramLoudnessBank:
         self.api.check(self.api.fn("program_loudness_bank_fetch_dynamics", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p])(
             self._h, stream_index, out.ctypes.data))
         return out[0]
+
+    # ---- include/omx/program_spectrum.h
+    def configure_spectrum(self, rule: SpectrumRule, channels: int):
+        """Set the rule and the channel count of the PCM the spectrum stage takes; allocates its records, sums and carried frames and
+        resets every stream.  Only while no stream of the stage holds frames: a new bank, or after reset_spectrum() of every
+        stream."""
+        c = rule.to_c()
+        self.api.check(self.api.fn("program_loudness_bank_spectrum_configure", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32])(
+            self._h, C.byref(c), channels))
+        self._spectrum_shape = (channels, rule.fft_size // 2 + 1)
+
+    def reset_spectrum(self, reset_mask: Optional[Sequence[int]] = None):
+        """The flagged streams of the spectrum stage start over with a zero record and zero sums (None: every stream)."""
+        mask = self._per_stream(reset_mask, np.uint8, "reset_mask")
+        self.api.check(self.api.fn("program_loudness_bank_spectrum_reset", C.c_int, [C.c_void_p, C.c_void_p])(
+            self._h, mask.ctypes.data if mask is not None else None))
+
+    def spectrum(self, d_in: int, frames_capacity: int, frames: Optional[Sequence[int]] = None,
+                 finish_mask: Optional[Sequence[int]] = None, stream: int = 0):
+        """Take frames[s] frames of d_in[s] (f32 [n_streams][frames_capacity][channels]) into the long-term spectrum of stream s, on
+        `stream`; d_in is only read.  A stream flagged in finish_mask completes its open transforms with zeros and takes no more
+        frames until reset_spectrum().  Returns (status, d_records, d_sums): status 1 when any stream brought a frame or was
+        finished, the device pointers to omx_program_spectrum_record[n_streams] (SPECTRUM_RECORD_DTYPE) and to the sums, f64
+        [n_streams][channels][fft_size / 2 + 1].  Both have the same bytes however the programme is cut into calls."""
+        fr = self._per_stream(frames, np.uint32, "frames")
+        fin = self._per_stream(finish_mask, np.uint8, "finish_mask")
+        rec, sums = C.c_void_p(), C.c_void_p()
+        f = self.api.fn("program_loudness_bank_spectrum", C.c_int,
+                        [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)])
+        status = self.api.check(f(self._h, C.c_void_p(d_in or 0), frames_capacity, fr.ctypes.data if fr is not None else None,
+                                  fin.ctypes.data if fin is not None else None, C.c_void_p(stream or 0), C.byref(rec), C.byref(sums)))
+        return status, rec.value or 0, sums.value or 0
+
+    def fetch_spectrum(self, stream_index: int):
+        """One stream's running record (a SPECTRUM_RECORD_DTYPE scalar) and its sums, f64 [channels][fft_size / 2 + 1]; synchronises."""
+        channels, bins = getattr(self, "_spectrum_shape", (1, 1))
+        rec, sums = np.zeros((1,), SPECTRUM_RECORD_DTYPE), np.zeros((channels, bins), np.float64)
+        self.api.check(self.api.fn("program_loudness_bank_fetch_spectrum", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p])(
+            self._h, stream_index, rec.ctypes.data, sums.ctypes.data))
+        return rec[0], sums
