@@ -52,16 +52,14 @@ int ProgramLoudnessBank::convolve_configure(uint32_t channels, const omx_program
             max_taps = std::max(max_taps, firs[f].n_taps);
         }
     if (delay_frames > max_taps - 1) return pl_refuse(who, "delay_frames > max_taps - 1");
-    if (convolve_)
-        for (const auto& m : convolve_->h_streams)
-            if (m.n != 0) return pl_refuse(who, "a stream of the stage holds frames (reset every stream first)");
+    if (convolve_ && carry_holds_frames(convolve_->h_streams)) return pl_refuse(who, "a stream of the stage holds frames (reset every stream first)");
     if (convolve_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
 
     auto cv = convolve_ ? std::move(convolve_) : std::make_unique<ProgramConvolve>();
     cv->channels = channels;
     cv->delay = delay_frames;
     cv->max_taps = max_taps;
-    cv->h_streams.assign(n_streams_, ProgramConvolve::Mirror{});
+    cv->h_streams.assign(n_streams_, CarryLedger{});
     cv->h_calls.assign(n_streams_, CvStreamCall{});
     cv->h_reach.assign(n_streams_, 0u);
     for (uint32_t s = 0; s < n_streams_; ++s) cv->h_reach[s] = std::max(longest[s], bypassed[s] ? delay_frames + 1 : 1u);
@@ -96,14 +94,7 @@ CvArgs ProgramLoudnessBank::convolve_args() const {
 int ProgramLoudnessBank::convolve_reset(const uint8_t* reset_mask) {
     if (!convolve_) return pl_refuse("convolve_reset", "the stage is not configured (omx_program_loudness_bank_convolve_configure)");
     ProgramConvolve& cv = *convolve_;
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        CvStreamCall c{};
-        if (!reset_mask || reset_mask[s]) {
-            cv.h_streams[s] = ProgramConvolve::Mirror{};
-            c.flags = kCvFlagClear;
-        }
-        cv.h_calls[s] = c;
-    }
+    carry_reset(cv.h_streams, cv.h_calls, reset_mask, [](const CarryLedger&) { return CvStreamCall{}; });
     pl_upload_table(cv.staging, cv.h_calls, cv.calls.ptr, last_stream_);
     const CvArgs a = convolve_args();
     launch_cv_begin(a, false, last_stream_);
@@ -121,44 +112,31 @@ int ProgramLoudnessBank::convolve(const float* d_in, uint64_t frames_capacity, c
     if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
         return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     CvArgs a = convolve_args();
-    bool any_in = false, any_out = false;
-    std::vector<CvStreamCall>& calls = cv.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
+    CarryTotals totals;
+    std::vector<CvStreamCall>& calls = cv.h_calls;  // (host scratch only: the ledger is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const ProgramConvolve::Mirror& m = cv.h_streams[s];
-        uint64_t f;
-        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
-        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
-        const bool flush = m.flushed || (flush_mask && flush_mask[s]);
-        const uint64_t n_new = m.n + f;
-        const uint64_t e_new = cv_emitted(cv.delay, n_new, m.e, flush);
-        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
+        const CarryLedger& m = cv.h_streams[s];
+        CarryStep step;
+        const auto emitted = [&](uint64_t n, uint64_t e, bool flush) { return carry_emitted(cv.delay, n, e, flush); };
+        if (const char* why = carry_step(m, frames, frames_capacity, flush_mask, s, out_capacity, emitted, step)) return pl_refuse(who, why);
         CvStreamCall c{};
         c.n_old = m.n;
         c.e_old = m.e;
         c.rel_e = (int64_t)(m.e + cv.delay) - (int64_t)m.n;
-        c.frames = (uint32_t)f;
-        c.emit = (uint32_t)(e_new - m.e);
+        c.frames = (uint32_t)step.frames;
+        c.emit = (uint32_t)step.emit;
         c.ring = a.history ? (uint32_t)(m.n % a.history) : 0u;
-        c.flags = flush ? kCvFlagFlush : 0u;
+        c.flags = step.flush ? kCarryFlagFlush : 0u;
         c.reach = cv.h_reach[s];
         calls[s] = c;
-        any_in = any_in || f != 0;
-        any_out = any_out || c.emit != 0;
-        a.max_frames = std::max(a.max_frames, c.frames);
-        a.max_emit = std::max(a.max_emit, c.emit);
+        totals.take(step);
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
-    // out of place only: a tile would read what another has already written
-    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
-    if (d_in && d_out && pl_ranges_overlap(d_in, frame_bytes * frames_capacity, d_out, frame_bytes * out_capacity))
-        return pl_refuse(who, "d_in and d_out overlap");
+    a.max_frames = totals.max_frames;
+    a.max_emit = totals.max_emit;
+    if (totals.null_pcm(d_in, d_out)) return pl_refuse(who, "null pcm");
+    if (pl_in_out_overlap(d_in, frames_capacity, d_out, out_capacity, n_streams_, a.channels, a.channels)) return pl_refuse(who, "d_in and d_out overlap");
 
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        ProgramConvolve::Mirror& m = cv.h_streams[s];
-        m.n += calls[s].frames;
-        m.e += calls[s].emit;
-        m.flushed = (calls[s].flags & kCvFlagFlush) != 0;
-    }
+    carry_commit(cv.h_streams, calls);
     last_stream_ = stream;
     pl_upload_table(cv.staging, calls, cv.calls.ptr, stream);
     a.in = d_in;
@@ -166,12 +144,12 @@ int ProgramLoudnessBank::convolve(const float* d_in, uint64_t frames_capacity, c
     a.frames_capacity = frames_capacity;
     a.out_capacity = out_capacity;
     launch_cv_begin(a, true, stream);
-    if (any_out) launch_cv_main(a, stream);
-    if (any_in) launch_cv_carry(a, stream);
+    if (totals.any_out) launch_cv_main(a, stream);
+    if (totals.any_in) launch_cv_carry(a, stream);
     launch_cv_finish(a, stream);
     OMX_HIP(hipGetLastError());
     if (d_convolved) *d_convolved = cv.records.ptr;
-    return any_out ? OMX_PRODUCED : OMX_NONE;
+    return totals.any_out ? OMX_PRODUCED : OMX_NONE;
 }
 
 int ProgramLoudnessBank::fetch_convolved(uint64_t stream_index, omx_program_convolve_record* dst) {

@@ -14,9 +14,6 @@
 
 namespace omx {
 
-constexpr uint32_t kCvFlagClear = 1u;  // the record is cleared before anything else (a reset)
-constexpr uint32_t kCvFlagFlush = 2u;  // x = 0 at and beyond the last frame taken; the stream is flushed afterwards
-
 // What one call does to one stream: made on the host (which mirrors N, E and the flushed flag), uploaded per call.
 struct CvStreamCall {
     uint64_t n_old;     // N before the call
@@ -25,7 +22,7 @@ struct CvStreamCall {
     uint32_t frames;    // F: frames taken in this call
     uint32_t emit;      // E' - E: frames written to d_out[s]
     uint32_t ring;      // n_old mod (max_taps - 1): the ring's slot of frame n_old
-    uint32_t flags;     // kCvFlag*
+    uint32_t flags;     // kCarryFlag*
     uint32_t reach;     // taps the stream's channels reach back over: its longest FIR, D + 1 where a channel is bypassed
     uint32_t _pad;
 };
@@ -60,11 +57,7 @@ void launch_cv_finish(const CvArgs& a, hipStream_t stream);
 // The stage's state: made by convolve_configure, nothing of it exists before.
 struct ProgramConvolve {
     uint32_t channels = 0, delay = 0, max_taps = 1;
-    struct Mirror {
-        uint64_t n = 0, e = 0;
-        bool flushed = false;
-    };
-    std::vector<Mirror> h_streams;
+    std::vector<CarryLedger> h_streams;
     std::vector<uint32_t> h_reach;  // [n_streams]
     std::vector<CvStreamCall> h_calls;
     DeviceBuffer<CvStreamCall> calls;

@@ -43,15 +43,6 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr uint32_t kCvR = kCvFramesPerThread, kCvKB = kCvTapBlock;
 static_assert(kCvR == 8 && kCvKB % kCvR == 0, "the window code below is written for runs of 8");
 
-__device__ __forceinline__ float cv_x_at(const CvArgs& a, const CvStreamCall& call, uint32_t s, int64_t rel, uint32_t c) {
-    if ((int64_t)call.n_old + rel < 0 || rel >= (int64_t)call.frames) return 0.0f;
-    if (rel >= 0) return a.in[((uint64_t)s * a.frames_capacity + (uint64_t)rel) * a.channels + c];
-    if (rel < -(int64_t)a.history) return 0.0f;  // (only the staging's alignment pad lies there: no tap reads it)
-    int64_t slot = (int64_t)call.ring + rel;
-    if (slot < 0) slot += a.history;
-    return a.ring[((uint64_t)s * a.history + (uint64_t)slot) * a.channels + c];
-}
-
 __device__ __forceinline__ omx_program_convolve_record cv_idle_record(const CvArgs& a) {
     omx_program_convolve_record r{};
     r.out_sample_peak_db = a.floor_db;
@@ -66,13 +57,8 @@ __global__ __launch_bounds__(64) void cv_begin_kernel(CvArgs a, uint32_t whole_c
     if (s >= a.n_streams) return;
     const CvStreamCall c = a.calls[s];
     omx_program_convolve_record r = a.records[s];
-    if (c.flags & kCvFlagClear) r = cv_idle_record(a);
-    if (whole_call) {
-        r.frames_in = c.n_old + c.frames;
-        r.frames_out = c.e_old + c.emit;
-        r.frames_written = c.emit;
-        r.state = (c.flags & kCvFlagFlush) ? OMX_CONVOLVE_FLUSHED : (r.frames_in != 0 ? OMX_CONVOLVE_RUNNING : OMX_CONVOLVE_IDLE);
-    }
+    if (c.flags & kCarryFlagClear) r = cv_idle_record(a);
+    if (whole_call) ps_begin_record<OMX_CONVOLVE_IDLE, OMX_CONVOLVE_RUNNING, OMX_CONVOLVE_FLUSHED>(r, c.n_old, c.e_old, c.frames, c.emit, c.flags);
     a.records[s] = r;
 }
 
@@ -179,7 +165,8 @@ __global__ __launch_bounds__(kCvThreads) void cv_main_kernel(CvArgs a, uint32_t 
                 }
             }
         } else {
-            for (uint32_t idx = tid; idx < n; idx += kCvThreads) stage(idx, cv_x_at(a, call, s, rel_base + (int64_t)(idx / C), idx % C));
+            // (further back than the ring reaches lies only the staging's alignment pad: no tap reads it)
+            for (uint32_t idx = tid; idx < n; idx += kCvThreads) stage(idx, ps_ring_x_at(a, call, s, rel_base + (int64_t)(idx / C), idx % C));
         }
         __syncthreads();
 
@@ -268,14 +255,9 @@ __global__ __launch_bounds__(kCvThreads) void cv_main_kernel(CvArgs a, uint32_t 
 __global__ __launch_bounds__(256) void cv_carry_kernel(CvArgs a, uint32_t s_base) {
     const uint32_t s = s_base + blockIdx.y;
     const CvStreamCall call = a.calls[s];
-    const uint32_t C = a.channels, e = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t nx = min(call.frames, a.history);
-    if (e < nx * C) {
-        const uint32_t fr = e / C, c = e - fr * C;
-        const uint64_t rel = (uint64_t)(call.frames - nx) + fr;
-        const uint64_t slot = ((uint64_t)call.ring + rel) % a.history;
-        a.ring[((uint64_t)s * a.history + slot) * C + c] = a.in[((uint64_t)s * a.frames_capacity + rel) * C + c];
-    }
+    const uint32_t C = a.channels;
+    ps_carry_row(a.ring + (uint64_t)s * a.history * C, a.history, C, call.ring, call.frames, blockIdx.x * 256 + threadIdx.x,
+                 [&](uint64_t rel, uint32_t c) { return a.in[((uint64_t)s * a.frames_capacity + rel) * C + c]; });
 }
 
 template <int C>
@@ -289,10 +271,10 @@ void cv_launch_main(const CvArgs& a, hipStream_t stream) {
 }  // namespace
 
 void launch_cv_begin(const CvArgs& a, bool whole_call, hipStream_t stream) {
-    hipLaunchKernelGGL(cv_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a, whole_call ? 1u : 0u);
+    ps_launch_per_stream(cv_begin_kernel, a.n_streams, stream, a, whole_call ? 1u : 0u);
 }
 void launch_cv_finish(const CvArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(cv_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(cv_finish_kernel, a.n_streams, stream, a);
 }
 void launch_cv_main(const CvArgs& a, hipStream_t stream) {
     switch (a.channels) {

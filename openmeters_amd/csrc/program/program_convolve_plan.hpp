@@ -10,6 +10,7 @@
 
 #include "../../../include/omx/program_convolve.h"
 #include "../../../include/omx/program_resample.h"  // OMX_RESAMPLE_I0_TERMS: the design shares the resampler's I0 series
+#include "program_carried.hpp"
 
 namespace omx {
 
@@ -36,19 +37,13 @@ inline int cv_plan(uint32_t channels, uint32_t max_taps, omx_program_convolve_in
     return OMX_NONE;
 }
 
-// E' of a stream with N frames taken (E emitted before), flushed or not
-inline uint64_t cv_emitted(uint32_t delay, uint64_t n, uint64_t e, bool flush) {
-    if (flush) return n;
-    return std::max(e, n > delay ? n - delay : 0);
-}
-
 inline int cv_frames(uint32_t delay, uint64_t n_before, uint64_t e_before, uint64_t frames, uint32_t flush, uint64_t* frames_out,
                      const char** why) {
     if (!frames_out) return cv_fail(why, "null frames_out");
     if (delay > OMX_CONVOLVE_MAX_TAPS - 1) return cv_fail(why, "delay above OMX_CONVOLVE_MAX_TAPS - 1");
     if (n_before > (1ull << 63) || frames > (1ull << 63) - n_before) return cv_fail(why, "frames_in_before + frames beyond 2^63");
     if (e_before > n_before) return cv_fail(why, "frames_out_before above frames_in_before");
-    *frames_out = cv_emitted(delay, n_before + frames, e_before, flush != 0) - e_before;
+    *frames_out = carry_emitted(delay, n_before + frames, e_before, flush != 0) - e_before;
     return OMX_NONE;
 }
 

@@ -45,9 +45,7 @@ int ProgramLoudnessBank::dynamics_configure(uint32_t channels, const omx_program
     for (uint32_t s = 0; curve_of_stream && s < n_streams_; ++s)
         if (curve_of_stream[s] != OMX_DYNAMICS_BYPASS && curve_of_stream[s] >= n_curves)
             return pl_refuse(who, "a curve index that is neither below n_curves nor OMX_DYNAMICS_BYPASS");
-    if (dynamics_)
-        for (const auto& m : dynamics_->h_streams)
-            if (m.n != 0) return pl_refuse(who, "a stream of the stage holds frames (reset every stream first)");
+    if (dynamics_ && carry_holds_frames(dynamics_->h_streams)) return pl_refuse(who, "a stream of the stage holds frames (reset every stream first)");
     if (dynamics_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
 
     auto dy = dynamics_ ? std::move(dynamics_) : std::make_unique<ProgramDynamics>();
@@ -119,16 +117,7 @@ DyArgs ProgramLoudnessBank::dynamics_args() const {
 int ProgramLoudnessBank::dynamics_reset(const uint8_t* reset_mask) {
     if (!dynamics_) return pl_refuse("dynamics_reset", "the stage is not configured (omx_program_loudness_bank_dynamics_configure)");
     ProgramDynamics& dy = *dynamics_;
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        ProgramDynamics::Stream& m = dy.h_streams[s];
-        DyStreamCall c = dy_call_of(m);
-        if (!reset_mask || reset_mask[s]) {
-            m.n = m.e = 0;
-            m.flushed = false;
-            c.flags = kDyFlagClear;
-        }
-        dy.h_calls[s] = c;
-    }
+    carry_reset(dy.h_streams, dy.h_calls, reset_mask, dy_call_of);
     pl_upload_table(dy.staging, dy.h_calls, dy.calls.ptr, last_stream_);
     const DyArgs a = dynamics_args();
     launch_dy_begin(a, false, last_stream_);
@@ -147,59 +136,51 @@ int ProgramLoudnessBank::dynamics(const float* d_in, const float* d_key, uint64_
     if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
         return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     DyArgs a = dynamics_args();
-    bool any_in = false, any_out = false, any_scan = false;
+    CarryTotals totals;
+    bool any_scan = false;
     uint64_t max_hold = 0;
-    std::vector<DyStreamCall>& calls = dy.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
+    std::vector<DyStreamCall>& calls = dy.h_calls;  // (host scratch only: the ledger is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
         const ProgramDynamics::Stream& m = dy.h_streams[s];
-        uint64_t f;
-        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
-        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
-        const bool flush = m.flushed || (flush_mask && flush_mask[s]);
         const uint32_t latency = m.attack - 1;
-        const uint64_t n_new = m.n + f, e_new = dy_emitted(latency, n_new, m.e, flush);
-        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
-        const uint64_t scan = m.flushed ? 0 : f + (flush ? latency : 0);
+        CarryStep step;
+        const auto emitted = [&](uint64_t n, uint64_t e, bool flush) { return carry_emitted(latency, n, e, flush); };
+        if (const char* why = carry_step(m, frames, frames_capacity, flush_mask, s, out_capacity, emitted, step)) return pl_refuse(who, why);
+        const uint64_t scan = m.flushed ? 0 : step.frames + (step.flush ? latency : 0);
         if (scan > 0xFFFFFFFFull) return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
         DyStreamCall c = dy_call_of(m);
         c.n_old = m.n;
-        c.frames = (uint32_t)f;
-        c.emit = (uint32_t)(e_new - m.e);
+        c.frames = (uint32_t)step.frames;
+        c.emit = (uint32_t)step.emit;
         c.held = (uint32_t)(m.n - m.e);
         c.scan = (uint32_t)scan;
-        c.flags = flush ? kDyFlagFlush : 0u;
+        c.flags = step.flush ? kCarryFlagFlush : 0u;
         c.ring_x = latency ? (uint32_t)(m.n % latency) : 0u;
         c.ring_g = c.window > 1 ? (uint32_t)(m.n % (c.window - 1)) : 0u;
         calls[s] = c;
-        any_in = any_in || f != 0;
-        any_out = any_out || c.emit != 0;
+        totals.take(step);
         any_scan = any_scan || scan != 0;
-        a.max_frames = std::max(a.max_frames, c.frames);
-        a.max_emit = std::max(a.max_emit, c.emit);
         a.max_scan = std::max(a.max_scan, c.scan);
         if (scan != 0) max_hold = std::max<uint64_t>(max_hold, scan + (c.window - std::min(c.window, kDyHoldMaxWindow)));
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
-    // out of place only: a tile would read what another has already written
-    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
-    const unsigned __int128 in_bytes = frame_bytes * frames_capacity, out_bytes = frame_bytes * out_capacity;
-    const unsigned __int128 trace_bytes = (unsigned __int128)n_streams_ * sizeof(float) * out_capacity;
-    const auto hits_input = [&](const void* p, unsigned __int128 bytes) {
-        return p && ((d_in && pl_ranges_overlap(d_in, in_bytes, p, bytes)) || (d_key && pl_ranges_overlap(d_key, in_bytes, p, bytes)));
+    a.max_frames = totals.max_frames;
+    a.max_emit = totals.max_emit;
+    if (totals.null_pcm(d_in, d_out)) return pl_refuse(who, "null pcm");
+    // out of place, for the key and the trace as well: neither output may share a byte with either input, nor with the other output
+    const uint32_t C = a.channels;
+    const auto hits_input = [&](const float* p, uint32_t frame_floats) {
+        return pl_in_out_overlap(d_in, frames_capacity, p, out_capacity, n_streams_, C, frame_floats) ||
+               pl_in_out_overlap(d_key, frames_capacity, p, out_capacity, n_streams_, C, frame_floats);
     };
-    if (hits_input(d_out, out_bytes)) return pl_refuse(who, "d_out overlaps d_in or d_key");
-    if (hits_input(d_gain_db, trace_bytes)) return pl_refuse(who, "d_gain_db overlaps d_in or d_key");
-    if (d_out && d_gain_db && pl_ranges_overlap(d_out, out_bytes, d_gain_db, trace_bytes)) return pl_refuse(who, "d_out and d_gain_db overlap");
+    if (hits_input(d_out, C)) return pl_refuse(who, "d_out overlaps d_in or d_key");
+    if (hits_input(d_gain_db, 1)) return pl_refuse(who, "d_gain_db overlaps d_in or d_key");
+    const unsigned __int128 trace_bytes = (unsigned __int128)n_streams_ * sizeof(float) * out_capacity;
+    if (d_out && d_gain_db && pl_ranges_overlap(d_out, trace_bytes * C, d_gain_db, trace_bytes)) return pl_refuse(who, "d_out and d_gain_db overlap");
     // the largest grid of the call is the apply pass's or the hold pass's: refused here, in front of the first change
     const uint64_t most_tiles = std::max<uint64_t>((a.max_emit + (uint64_t)kDySmoothTile - 1) / kDySmoothTile, (max_hold + kDyHoldTile - 1) / kDyHoldTile);
     if (max_hold > 0xFFFFFFFFull || most_tiles * n_streams_ > 0x7FFFFFFFull) unsupported("programme dynamics: call too long for one launch");
 
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        ProgramDynamics::Stream& m = dy.h_streams[s];
-        m.n += calls[s].frames;
-        m.e += calls[s].emit;
-        m.flushed = (calls[s].flags & kDyFlagFlush) != 0;
-    }
+    carry_commit(dy.h_streams, calls);
     last_stream_ = stream;
     pl_upload_table(dy.staging, calls, dy.calls.ptr, stream);
     a.in = d_in;
@@ -213,7 +194,7 @@ int ProgramLoudnessBank::dynamics(const float* d_in, const float* d_key, uint64_
     a.r_row = (a.max_scan + 1u) & ~1u;
     a.t_row = (a.max_scan + kDyReleaseTile - 1) / kDyReleaseTile;
     launch_dy_begin(a, true, stream);
-    if (any_in) {
+    if (totals.any_in) {
         dy.gt.reserve((size_t)n_streams_ * a.g_row);
         a.gt = dy.gt.ptr;
         launch_dy_level(a, stream);
@@ -231,12 +212,12 @@ int ProgramLoudnessBank::dynamics(const float* d_in, const float* d_key, uint64_
         launch_dy_release(a, stream);
         launch_dy_chain(a, stream);
     }
-    if (any_out) launch_dy_apply(a, stream);
-    if (any_in) launch_dy_carry(a, stream);
+    if (totals.any_out) launch_dy_apply(a, stream);
+    if (totals.any_in) launch_dy_carry(a, stream);
     launch_dy_finish(a, stream);
     OMX_HIP(hipGetLastError());
     if (d_records) *d_records = dy.records.ptr;
-    return any_out ? OMX_PRODUCED : OMX_NONE;
+    return totals.any_out ? OMX_PRODUCED : OMX_NONE;
 }
 
 int ProgramLoudnessBank::fetch_dynamics(uint64_t stream_index, omx_program_dynamics_record* dst) {

@@ -15,9 +15,6 @@
 
 namespace omx {
 
-constexpr uint32_t kDyFlagClear = 1u;   // the record, the carry and the rings' meaning are cleared before anything else (a reset)
-constexpr uint32_t kDyFlagFlush = 4u;   // Gt = T[0] at and beyond the last frame taken; the stream is flushed afterwards
-
 // What one call does to one stream: made on the host (which mirrors N, E and the flushed flag), uploaded per call.
 struct DyStreamCall {
     uint64_t n_old;       // N before the call
@@ -26,7 +23,7 @@ struct DyStreamCall {
     uint32_t emit;        // E' - E: frames written to d_out[s]
     uint32_t held;        // N - E before the call (<= LA): emitted frame f of the call is x[n_old - held + f]
     uint32_t scan;        // values of r the call computes: F, and LA more with the flush
-    uint32_t flags;       // kDyFlag*
+    uint32_t flags;       // kCarryFlag*
     uint32_t curve;       // row of the curve table (a bypassed stream: the row of zeros), and what the record reports in curve_index
     uint32_t curve_index;
     uint32_t mask;        // detector_mask
@@ -79,9 +76,7 @@ void launch_dy_finish(const DyArgs& a, hipStream_t stream);
 // The stage's state: made by dynamics_configure, nothing of it exists before.
 struct ProgramDynamics {
     uint32_t channels = 0, n_curves = 0, max_attack = 1, max_latency = 1, max_history = 1;
-    struct Stream {
-        uint64_t n = 0, e = 0;
-        bool flushed = false;
+    struct Stream : CarryLedger {
         uint32_t curve = 0, curve_index = 0, mask = 1, attack = 1, hold = 0;
         int64_t step = 1;
     };

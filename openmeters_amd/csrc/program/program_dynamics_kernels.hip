@@ -96,16 +96,11 @@ __global__ __launch_bounds__(64) void dy_begin_kernel(DyArgs a, uint32_t whole_c
     if (s >= a.n_streams) return;
     const DyStreamCall c = a.calls[s];
     omx_program_dynamics_record r = a.records[s];
-    if (c.flags & kDyFlagClear) {
+    if (c.flags & kCarryFlagClear) {
         r = dy_idle_record(a, c);
         a.carry[s] = (long long)dy_first_gain(a, c) * 65536;
     }
-    if (whole_call) {
-        r.frames_in = c.n_old + c.frames;
-        r.frames_out = c.n_old - c.held + c.emit;
-        r.frames_written = c.emit;
-        r.state = (c.flags & kDyFlagFlush) ? OMX_DYNAMICS_FLUSHED : (r.frames_in != 0 ? OMX_DYNAMICS_RUNNING : OMX_DYNAMICS_IDLE);
-    }
+    if (whole_call) ps_begin_record<OMX_DYNAMICS_IDLE, OMX_DYNAMICS_RUNNING, OMX_DYNAMICS_FLUSHED>(r, c.n_old, c.n_old - c.held, c.frames, c.emit, c.flags);
     a.records[s] = r;
 }
 
@@ -438,24 +433,13 @@ __global__ __launch_bounds__(kDyThreads) void dy_carry_kernel(DyArgs a, uint32_t
     const uint32_t s = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
     const DyStreamCall call = a.calls[s];
     const uint32_t C = a.channels, e = tile * kDyThreads + threadIdx.x;
-    const uint32_t LA = call.attack - 1, GH = call.window - 1;
-    const uint32_t nx = min(call.frames, LA), ng = min(call.frames, GH);
-    if (e < nx * C) {
-        const uint32_t fr = e / C, c = e - fr * C;
-        const uint64_t rel = (uint64_t)(call.frames - nx) + fr;
-        const uint64_t slot = ((uint64_t)call.ring_x + rel) % LA;
-        a.ring_x[((uint64_t)s * a.max_latency + slot) * C + c] = a.in[((uint64_t)s * a.frames_capacity + rel) * C + c];
-    }
-    if (e < nx) {
-        const uint64_t rel = (uint64_t)(call.frames - nx) + e;
-        const uint64_t slot = ((uint64_t)call.ring_x + rel) % LA;
-        a.ring_r[(uint64_t)s * a.max_latency + slot] = dy_r_here(a, call, s, rel);
-    }
-    if (e < ng) {
-        const uint64_t rel = (uint64_t)(call.frames - ng) + e;
-        const uint64_t slot = ((uint64_t)call.ring_g + rel) % GH;
-        a.ring_g[(uint64_t)s * a.max_history + slot] = a.gt[(uint64_t)s * a.g_row + rel];
-    }
+    const uint32_t LA = call.attack - 1, GH = call.window - 1;  // (the rows are as long as the bank's longest)
+    ps_carry_row(a.ring_x + (uint64_t)s * a.max_latency * C, LA, C, call.ring_x, call.frames, e,
+                 [&](uint64_t rel, uint32_t c) { return a.in[((uint64_t)s * a.frames_capacity + rel) * C + c]; });
+    ps_carry_row(a.ring_r + (uint64_t)s * a.max_latency, LA, 1u, call.ring_x, call.frames, e,
+                 [&](uint64_t rel, uint32_t) { return dy_r_here(a, call, s, rel); });
+    ps_carry_row(a.ring_g + (uint64_t)s * a.max_history, GH, 1u, call.ring_g, call.frames, e,
+                 [&](uint64_t rel, uint32_t) { return a.gt[(uint64_t)s * a.g_row + rel]; });
 }
 
 uint32_t dy_grid(const DyArgs& a, uint64_t tiles) {
@@ -467,10 +451,10 @@ uint32_t dy_grid(const DyArgs& a, uint64_t tiles) {
 }  // namespace
 
 void launch_dy_begin(const DyArgs& a, bool whole_call, hipStream_t stream) {
-    hipLaunchKernelGGL(dy_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a, whole_call ? 1u : 0u);
+    ps_launch_per_stream(dy_begin_kernel, a.n_streams, stream, a, whole_call ? 1u : 0u);
 }
 void launch_dy_finish(const DyArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(dy_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(dy_finish_kernel, a.n_streams, stream, a);
 }
 void launch_dy_level(const DyArgs& a, hipStream_t stream) {
     const uint32_t tiles = (a.max_frames + kDyLevelTile - 1) / kDyLevelTile;

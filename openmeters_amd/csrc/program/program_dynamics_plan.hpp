@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../../include/omx/program_dynamics.h"
+#include "program_carried.hpp"
 
 namespace omx {
 
@@ -115,19 +116,13 @@ inline int dy_latency(const omx_program_dynamics_curve* c, uint32_t* frames, con
     return OMX_NONE;
 }
 
-// E' of a stream with N frames taken (E emitted before), flushed or not
-inline uint64_t dy_emitted(uint32_t latency, uint64_t n, uint64_t e, bool flush) {
-    if (flush) return n;
-    return std::max(e, n > latency ? n - latency : 0);
-}
-
 inline int dy_frames(uint32_t latency, uint64_t n_before, uint64_t e_before, uint64_t frames, uint32_t flush, uint64_t* frames_out,
                      const char** why) {
     if (!frames_out) return dy_fail(why, "null frames_out");
     if (latency > OMX_DYNAMICS_MAX_ATTACK - 1) return dy_fail(why, "latency above 4095");
     if (n_before > (1ull << 63) || frames > (1ull << 63) - n_before) return dy_fail(why, "frames_in_before + frames beyond 2^63");
     if (e_before > n_before) return dy_fail(why, "frames_out_before above frames_in_before");
-    *frames_out = dy_emitted(latency, n_before + frames, e_before, flush != 0) - e_before;
+    *frames_out = carry_emitted(latency, n_before + frames, e_before, flush != 0) - e_before;
     return OMX_NONE;
 }
 

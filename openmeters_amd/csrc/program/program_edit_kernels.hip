@@ -266,10 +266,10 @@ void ed_launch_main(const EdArgs& a, hipStream_t stream) {
 }  // namespace
 
 void launch_ed_begin(const EdArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(ed_begin_kernel, dim3((a.n_out + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(ed_begin_kernel, a.n_out, stream, a);
 }
 void launch_ed_finish(const EdArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(ed_finish_kernel, dim3((a.n_out + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(ed_finish_kernel, a.n_out, stream, a);
 }
 void launch_ed_main(const EdArgs& a, hipStream_t stream) {
     switch (a.channels) {

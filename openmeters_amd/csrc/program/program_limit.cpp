@@ -24,16 +24,15 @@ int ProgramLoudnessBank::limiter_configure(const omx_program_limit_rule* rule, u
     if (!pl_channels_ok(channels)) return pl_refuse("limiter_configure", "channels outside 1 .. 8");
     const float rate = sanitize_sample_rate(sample_rate);
     if (rate < kPlMinRate) unsupported("programme loudness below 3364 Hz: the K-weighting filter has poles outside the unit circle");
-    if (limiter_)
-        for (const auto& m : limiter_->h_streams)
-            if (m.n != 0) return pl_refuse("limiter_configure", "a stream of the limiter holds frames (reset every stream first)");
+    if (limiter_ && carry_holds_frames(limiter_->h_streams))
+        return pl_refuse("limiter_configure", "a stream of the limiter holds frames (reset every stream first)");
     if (limiter_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
     auto lim = limiter_ ? std::move(limiter_) : std::make_unique<ProgramLimiter>();
     lim->rule = *rule;
     lim->channels = channels;
     lim->rate = rate;
     lim->ceiling = (float)std::pow(10.0, (double)rule->ceiling_db / 20.0);
-    lim->h_streams.assign(n_streams_, ProgramLimiter::Mirror{});
+    lim->h_streams.assign(n_streams_, CarryLedger{});
     lim->h_calls.assign(n_streams_, LmStreamCall{});
     const uint32_t A = rule->attack_frames, W = A + 24 + rule->release_hold_frames;
     lim->calls.reserve(n_streams_);
@@ -71,14 +70,7 @@ LmArgs ProgramLoudnessBank::limiter_args() const {
 int ProgramLoudnessBank::limiter_reset(const uint8_t* reset_mask) {
     if (!limiter_) return pl_refuse("limiter_reset", "the limiter is not configured (omx_program_loudness_bank_limiter_configure)");
     ProgramLimiter& lim = *limiter_;
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        LmStreamCall c{};
-        if (!reset_mask || reset_mask[s]) {
-            lim.h_streams[s] = ProgramLimiter::Mirror{};
-            c.flags = kLmFlagClear;
-        }
-        lim.h_calls[s] = c;
-    }
+    carry_reset(lim.h_streams, lim.h_calls, reset_mask, [](const CarryLedger&) { return LmStreamCall{}; });
     pl_upload_table(lim.staging, lim.h_calls, lim.calls.ptr, last_stream_);
     const LmArgs a = limiter_args();
     launch_lm_begin(a, false, last_stream_);
@@ -97,48 +89,36 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
     if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
         return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     LmArgs a = limiter_args();
-    bool any_in = false, any_out = false, named = false;
-    std::vector<LmStreamCall>& calls = lim.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
+    CarryTotals totals;
+    bool named = false;
+    std::vector<LmStreamCall>& calls = lim.h_calls;  // (host scratch only: the ledger is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const ProgramLimiter::Mirror& m = lim.h_streams[s];
-        uint64_t f;
-        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
-        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
-        const uint64_t index = gain_of_stream ? gain_of_stream[s] : s;
+        const CarryLedger& m = lim.h_streams[s];
+        CarryStep step;
+        const auto emitted = [&](uint64_t n, uint64_t e, bool flush) { return carry_emitted(a.latency, n, e, flush); };
+        if (const char* why = carry_step(m, frames, frames_capacity, flush_mask, s, out_capacity, emitted, step)) return pl_refuse(who, why);
+        const uint64_t index = gain_of_stream ? gain_of_stream[s] : s;  // (tested behind the shared step: a stream wrong in both ways is refused for its frames)
         if (index != OMX_PROGRAM_UNITY_GAIN && index >= n_gains) return pl_refuse(who, "gain index at or above n_gains");
-        const bool flush = m.flushed || (flush_mask && flush_mask[s]);
-        const uint64_t n_new = m.n + f;
-        const uint64_t e_new = flush ? n_new : std::max<uint64_t>(m.e, n_new > a.latency ? n_new - a.latency : 0);
-        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
         LmStreamCall c{};
         c.n_old = m.n;
-        c.frames = (uint32_t)f;
-        c.emit = (uint32_t)(e_new - m.e);
+        c.frames = (uint32_t)step.frames;
+        c.emit = (uint32_t)step.emit;
         c.held = (uint32_t)(m.n - m.e);
         c.gain_index = (uint32_t)index;
-        c.flags = (flush ? kLmFlagFlush : 0u) | (m.n == 0 && f != 0 ? kLmFlagLatch : 0u);
+        c.flags = (step.flush ? kCarryFlagFlush : 0u) | (m.n == 0 && step.frames != 0 ? kLmFlagLatch : 0u);
         c.ring_x = (uint32_t)(m.n % a.latency);
         c.ring_q = (uint32_t)(m.n % a.q_history);
         calls[s] = c;
-        any_in = any_in || f != 0;
-        any_out = any_out || c.emit != 0;
+        totals.take(step);
         named = named || ((c.flags & kLmFlagLatch) && index != OMX_PROGRAM_UNITY_GAIN);
-        a.max_frames = std::max(a.max_frames, c.frames);
-        a.max_emit = std::max(a.max_emit, c.emit);
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
+    a.max_frames = totals.max_frames;
+    a.max_emit = totals.max_emit;
+    if (totals.null_pcm(d_in, d_out)) return pl_refuse(who, "null pcm");
     if (named && !d_gains) return pl_refuse(who, "null gain records while a stream names one");
-    // out of place only: a tile would read what another has already written
-    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
-    if (d_in && d_out && pl_ranges_overlap(d_in, frame_bytes * frames_capacity, d_out, frame_bytes * out_capacity))
-        return pl_refuse(who, "d_in and d_out overlap");
+    if (pl_in_out_overlap(d_in, frames_capacity, d_out, out_capacity, n_streams_, a.channels, a.channels)) return pl_refuse(who, "d_in and d_out overlap");
 
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        ProgramLimiter::Mirror& m = lim.h_streams[s];
-        m.n += calls[s].frames;
-        m.e += calls[s].emit;
-        m.flushed = (calls[s].flags & kLmFlagFlush) != 0;
-    }
+    carry_commit(lim.h_streams, calls);
     last_stream_ = stream;
     pl_upload_table(lim.staging, calls, lim.calls.ptr, stream);
     a.in = d_in;
@@ -150,12 +130,12 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
     a.e_row = a.max_emit;
     a.m_row = a.max_emit + (a.attack - 1) + (a.window - a.hold_len);
     launch_lm_begin(a, true, stream);
-    if (any_in) {
+    if (totals.any_in) {
         lim.q.reserve((size_t)n_streams_ * a.q_row);
         a.q = lim.q.ptr;
         launch_lm_level(a, stream);
     }
-    if (any_out) {
+    if (totals.any_out) {
         lim.held_min.reserve((size_t)n_streams_ * a.m_row);
         lim.envelope.reserve((size_t)n_streams_ * a.e_row);
         a.held_min = lim.held_min.ptr;
@@ -164,11 +144,11 @@ int ProgramLoudnessBank::apply_limited(const float* d_in, uint64_t frames_capaci
         launch_lm_smooth(a, stream);
         launch_lm_apply(a, stream);
     }
-    if (any_in) launch_lm_carry(a, stream);
+    if (totals.any_in) launch_lm_carry(a, stream);
     launch_lm_finish(a, stream);
     OMX_HIP(hipGetLastError());
     if (d_limited) *d_limited = lim.records.ptr;
-    return any_out ? OMX_PRODUCED : OMX_NONE;
+    return totals.any_out ? OMX_PRODUCED : OMX_NONE;
 }
 
 int ProgramLoudnessBank::fetch_limited(uint64_t stream_index, omx_program_limit_record* dst) {

@@ -10,6 +10,7 @@
 
 #include "../common.hpp"
 #include "../../../include/omx/program_limit.h"
+#include "program_carried.hpp"
 
 namespace omx {
 
@@ -22,9 +23,7 @@ constexpr uint32_t kLmApplyTileVecs = kLmApplyThreads * kLmApplyInFlight, kLmApp
 constexpr uint32_t kLmHistory = 23;       // frames in front of a frame that its level reads (the 2x interpolator has 24 taps)
 constexpr uint32_t kLmUnity = 1u << 24;   // q of a frame at or below the ceiling
 
-constexpr uint32_t kLmFlagClear = 1u;     // the record and the latch are cleared before anything else (a reset)
-constexpr uint32_t kLmFlagLatch = 2u;     // the stream takes its first frame: the gain is read
-constexpr uint32_t kLmFlagFlush = 4u;     // q = 2^24 at and beyond the last frame taken; the stream is flushed afterwards
+constexpr uint32_t kLmFlagLatch = 4u;     // the stream takes its first frame: the gain is read (beside kCarryFlag*)
 
 // What one call does to one stream: made on the host (which mirrors N, E and the flushed flag), uploaded per call.
 struct LmStreamCall {
@@ -33,7 +32,7 @@ struct LmStreamCall {
     uint32_t emit;        // E' - E: frames written to d_out[s]
     uint32_t held;        // N - E before the call (<= LA): emitted frame f of the call is x[n_old - held + f]
     uint32_t gain_index;  // read with kLmFlagLatch
-    uint32_t flags;       // kLmFlag*
+    uint32_t flags;       // kCarryFlag*, kLmFlagLatch
     uint32_t ring_x;      // n_old mod LA: the PCM ring's slot of frame n_old
     uint32_t ring_q;      // n_old mod history length of q
     uint32_t _pad;
@@ -77,11 +76,7 @@ struct ProgramLimiter {
     omx_program_limit_rule rule{};
     uint32_t channels = 0;
     float rate = 0.0f, ceiling = 0.0f;
-    struct Mirror {
-        uint64_t n = 0, e = 0;
-        bool flushed = false;
-    };
-    std::vector<Mirror> h_streams;
+    std::vector<CarryLedger> h_streams;
     std::vector<LmStreamCall> h_calls;
     DeviceBuffer<LmStreamCall> calls;
     DeviceBuffer<omx_program_limit_record> records;

@@ -62,17 +62,12 @@ __global__ __launch_bounds__(64) void lm_begin_kernel(LmArgs a, uint32_t whole_c
     if (s >= a.n_streams) return;
     const LmStreamCall c = a.calls[s];
     omx_program_limit_record r = a.records[s];
-    if (c.flags & kLmFlagClear) r = lm_idle_record(a);
+    if (c.flags & kCarryFlagClear) r = lm_idle_record(a);
     if (c.flags & kLmFlagLatch) {
         r.gain = c.gain_index == OMX_PROGRAM_UNITY_GAIN ? 1.0f : a.gains[c.gain_index].gain;
         r.gain_index = c.gain_index;
     }
-    if (whole_call) {
-        r.frames_in = c.n_old + c.frames;
-        r.frames_out = c.n_old - c.held + c.emit;
-        r.frames_written = c.emit;
-        r.state = (c.flags & kLmFlagFlush) ? OMX_LIMIT_FLUSHED : (r.frames_in != 0 ? OMX_LIMIT_RUNNING : OMX_LIMIT_IDLE);
-    }
+    if (whole_call) ps_begin_record<OMX_LIMIT_IDLE, OMX_LIMIT_RUNNING, OMX_LIMIT_FLUSHED>(r, c.n_old, c.n_old - c.held, c.frames, c.emit, c.flags);
     a.records[s] = r;
 }
 
@@ -343,18 +338,10 @@ __global__ __launch_bounds__(256) void lm_carry_kernel(LmArgs a, uint32_t n_tile
     const uint32_t s = blockIdx.x / n_tiles, tile = blockIdx.x % n_tiles;
     const LmStreamCall call = a.calls[s];
     const uint32_t C = a.channels, e = tile * 256 + threadIdx.x;
-    const uint32_t nx = min(call.frames, a.latency), nq = min(call.frames, a.q_history);
-    if (e < nx * C) {
-        const uint32_t fr = e / C, c = e - fr * C;
-        const uint64_t rel = (uint64_t)(call.frames - nx) + fr;
-        const uint64_t slot = ((uint64_t)call.ring_x + rel) % a.latency;
-        a.ring_x[((uint64_t)s * a.latency + slot) * C + c] = a.in[((uint64_t)s * a.frames_capacity + rel) * C + c];
-    }
-    if (e < nq) {
-        const uint64_t rel = (uint64_t)(call.frames - nq) + e;
-        const uint64_t slot = ((uint64_t)call.ring_q + rel) % a.q_history;
-        a.ring_q[(uint64_t)s * a.q_history + slot] = a.q[(uint64_t)s * a.q_row + rel];
-    }
+    ps_carry_row(a.ring_x + (uint64_t)s * a.latency * C, a.latency, C, call.ring_x, call.frames, e,
+                 [&](uint64_t rel, uint32_t c) { return a.in[((uint64_t)s * a.frames_capacity + rel) * C + c]; });
+    ps_carry_row(a.ring_q + (uint64_t)s * a.q_history, a.q_history, 1u, call.ring_q, call.frames, e,
+                 [&](uint64_t rel, uint32_t) { return a.q[(uint64_t)s * a.q_row + rel]; });
 }
 
 uint32_t lm_grid(const LmArgs& a, uint64_t tiles) {
@@ -366,10 +353,10 @@ uint32_t lm_grid(const LmArgs& a, uint64_t tiles) {
 }  // namespace
 
 void launch_lm_begin(const LmArgs& a, bool whole_call, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a, whole_call ? 1u : 0u);
+    ps_launch_per_stream(lm_begin_kernel, a.n_streams, stream, a, whole_call ? 1u : 0u);
 }
 void launch_lm_finish(const LmArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(lm_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(lm_finish_kernel, a.n_streams, stream, a);
 }
 void launch_lm_level(const LmArgs& a, hipStream_t stream) {
     const uint32_t tiles = (a.max_frames + kLmLevelTile - 1) / kLmLevelTile;

@@ -280,10 +280,10 @@ void mx_launch_main(const MxArgs& a, hipStream_t stream) {
 }  // namespace
 
 void launch_mx_begin(const MxArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(mx_begin_kernel, dim3((a.n_out + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(mx_begin_kernel, a.n_out, stream, a);
 }
 void launch_mx_finish(const MxArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(mx_finish_kernel, dim3((a.n_out + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(mx_finish_kernel, a.n_out, stream, a);
 }
 void launch_mx_main(const MxArgs& a, hipStream_t stream) {
     switch (a.channels) {

@@ -140,10 +140,10 @@ void launch_pn_plan_groups(const omx_program_gain_rule& rule, const omx_program_
                        floor_db);
 }
 void launch_pn_begin(const PnApplyArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pn_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(pn_begin_kernel, a.n_streams, stream, a);
 }
 void launch_pn_finish(const PnApplyArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pn_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(pn_finish_kernel, a.n_streams, stream, a);
 }
 void launch_pn_tiles(const PnApplyArgs& a, uint64_t max_n, bool non_temporal, hipStream_t stream) {
     // tiles of the longest row (a row's body is at most max_n / 4 vectors; tile 0 exists for every row that brings a float)

@@ -428,10 +428,10 @@ void launch_pc_import(const PcArgs& a, uint64_t max_n, hipStream_t stream) {
     });
 }
 void launch_pc_export_begin(const PcArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pc_export_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(pc_export_begin_kernel, a.n_streams, stream, a);
 }
 void launch_pc_export_finish(const PcArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pc_export_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(pc_export_finish_kernel, a.n_streams, stream, a);
 }
 void launch_pc_export(const PcArgs& a, uint64_t max_n, hipStream_t stream) {
     const bool tpdf = a.dither == OMX_DITHER_TPDF;

@@ -199,10 +199,10 @@ void rm_launch_main(const RmArgs& a, hipStream_t stream) {
 }  // namespace
 
 void launch_rm_begin(const RmArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(rm_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(rm_begin_kernel, a.n_streams, stream, a);
 }
 void launch_rm_finish(const RmArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(rm_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(rm_finish_kernel, a.n_streams, stream, a);
 }
 void launch_rm_main(const RmArgs& a, hipStream_t stream) {
     switch (a.channels_in) {

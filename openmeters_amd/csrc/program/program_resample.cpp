@@ -95,15 +95,13 @@ int ProgramLoudnessBank::resampler_configure(const omx_program_resample_rule* ru
     const int planned = rs_plan(rule, &info);
     if (planned != OMX_NONE) return planned;
     if (!pl_channels_ok(channels)) return pl_refuse(who, "channels outside 1 .. 8");
-    if (resampler_)
-        for (const auto& m : resampler_->h_streams)
-            if (m.n != 0) return pl_refuse(who, "a stream of the resampler holds frames (reset every stream first)");
+    if (resampler_ && carry_holds_frames(resampler_->h_streams)) return pl_refuse(who, "a stream of the resampler holds frames (reset every stream first)");
     if (resampler_) OMX_HIP(hipStreamSynchronize(last_stream_));  // (a pass that reads the old buffers may still be in flight)
     auto rs = resampler_ ? std::move(resampler_) : std::make_unique<ProgramResampler>();
     rs->rule = *rule;
     rs->info = info;
     rs->channels = channels;
-    rs->h_streams.assign(n_streams_, ProgramResampler::Mirror{});
+    rs->h_streams.assign(n_streams_, CarryLedger{});
     rs->h_calls.assign(n_streams_, RsStreamCall{});
     std::vector<float> taps(info.table_floats);
     rs_build_taps(*rule, info, taps.data());
@@ -142,14 +140,7 @@ RsArgs ProgramLoudnessBank::resampler_args() const {
 int ProgramLoudnessBank::resampler_reset(const uint8_t* reset_mask) {
     if (!resampler_) return pl_refuse("resampler_reset", "the resampler is not configured (omx_program_loudness_bank_resampler_configure)");
     ProgramResampler& rs = *resampler_;
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        RsStreamCall c{};
-        if (!reset_mask || reset_mask[s]) {
-            rs.h_streams[s] = ProgramResampler::Mirror{};
-            c.flags = kRsFlagClear;
-        }
-        rs.h_calls[s] = c;
-    }
+    carry_reset(rs.h_streams, rs.h_calls, reset_mask, [](const CarryLedger&) { return RsStreamCall{}; });
     pl_upload_table(rs.staging, rs.h_calls, rs.calls.ptr, last_stream_);
     const RsArgs a = resampler_args();
     launch_rs_begin(a, false, last_stream_);
@@ -167,46 +158,33 @@ int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, c
     if (!pl_capacity_ok(frames_capacity) || !pl_capacity_ok(out_capacity))
         return pl_refuse(who, "frames_capacity or out_capacity beyond 2^32 - 1");
     RsArgs a = resampler_args();
-    bool any_in = false, any_out = false;
-    std::vector<RsStreamCall>& calls = rs.h_calls;  // (host scratch only: the mirror is committed below, after the last check)
+    CarryTotals totals;
+    std::vector<RsStreamCall>& calls = rs.h_calls;  // (host scratch only: the ledger is committed below, after the last check)
     for (uint32_t s = 0; s < n_streams_; ++s) {
-        const ProgramResampler::Mirror& m = rs.h_streams[s];
-        uint64_t f;
-        if (!pl_stream_frames(who, frames, frames_capacity, s, f)) return OMX_ERR_INVALID;
-        if (f != 0 && m.flushed) return pl_refuse(who, "frames for a flushed stream (reset it first)");
-        const bool flush = m.flushed || (flush_mask && flush_mask[s]);
-        const uint64_t n_new = m.n + f;
-        const uint64_t e_new = rs_emitted(rs.info, n_new, m.e, flush);
-        if (e_new - m.e > out_capacity) return pl_refuse(who, "a stream would emit more than out_capacity frames");
+        const CarryLedger& m = rs.h_streams[s];
+        CarryStep step;
+        const auto emitted = [&](uint64_t n, uint64_t e, bool flush) { return rs_emitted(rs.info, n, e, flush); };
+        if (const char* why = carry_step(m, frames, frames_capacity, flush_mask, s, out_capacity, emitted, step)) return pl_refuse(who, why);
         const unsigned __int128 pos = (unsigned __int128)m.e * a.M;
         RsStreamCall c{};
         c.n_old = m.n;
         c.e_old = m.e;
         c.rel_e = (int64_t)(uint64_t)(pos / a.L) - (int64_t)m.n;
         c.phase_e = (uint32_t)(pos % a.L);
-        c.frames = (uint32_t)f;
-        c.emit = (uint32_t)(e_new - m.e);
+        c.frames = (uint32_t)step.frames;
+        c.emit = (uint32_t)step.emit;
         c.ring = (uint32_t)(m.n % a.history);
-        c.flags = flush ? kRsFlagFlush : 0u;
+        c.flags = step.flush ? kCarryFlagFlush : 0u;
         calls[s] = c;
-        any_in = any_in || f != 0;
-        any_out = any_out || c.emit != 0;
-        a.max_frames = std::max(a.max_frames, c.frames);
-        a.max_emit = std::max(a.max_emit, c.emit);
+        totals.take(step);
     }
-    if ((any_in && !d_in) || (any_out && !d_out)) return pl_refuse(who, "null pcm");
+    a.max_frames = totals.max_frames;
+    a.max_emit = totals.max_emit;
+    if (totals.null_pcm(d_in, d_out)) return pl_refuse(who, "null pcm");
     if (((uint64_t)a.max_emit + a.tile - 1) / a.tile * kRsThreads > 0xFFFFFFFFull) unsupported("programme resampler: call too long for one launch");
-    // out of place only: a tile would read what another has already written
-    const unsigned __int128 frame_bytes = (unsigned __int128)n_streams_ * a.channels * sizeof(float);
-    if (d_in && d_out && pl_ranges_overlap(d_in, frame_bytes * frames_capacity, d_out, frame_bytes * out_capacity))
-        return pl_refuse(who, "d_in and d_out overlap");
+    if (pl_in_out_overlap(d_in, frames_capacity, d_out, out_capacity, n_streams_, a.channels, a.channels)) return pl_refuse(who, "d_in and d_out overlap");
 
-    for (uint32_t s = 0; s < n_streams_; ++s) {
-        ProgramResampler::Mirror& m = rs.h_streams[s];
-        m.n += calls[s].frames;
-        m.e += calls[s].emit;
-        m.flushed = (calls[s].flags & kRsFlagFlush) != 0;
-    }
+    carry_commit(rs.h_streams, calls);
     last_stream_ = stream;
     pl_upload_table(rs.staging, calls, rs.calls.ptr, stream);
     a.in = d_in;
@@ -214,12 +192,12 @@ int ProgramLoudnessBank::resample(const float* d_in, uint64_t frames_capacity, c
     a.frames_capacity = frames_capacity;
     a.out_capacity = out_capacity;
     launch_rs_begin(a, true, stream);
-    if (any_out) launch_rs_main(a, stream);
-    if (any_in) launch_rs_carry(a, stream);
+    if (totals.any_out) launch_rs_main(a, stream);
+    if (totals.any_in) launch_rs_carry(a, stream);
     launch_rs_finish(a, stream);
     OMX_HIP(hipGetLastError());
     if (d_resampled) *d_resampled = rs.records.ptr;
-    return any_out ? OMX_PRODUCED : OMX_NONE;
+    return totals.any_out ? OMX_PRODUCED : OMX_NONE;
 }
 
 int ProgramLoudnessBank::fetch_resampled(uint64_t stream_index, omx_program_resample_record* dst) {

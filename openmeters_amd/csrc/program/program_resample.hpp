@@ -10,6 +10,7 @@
 
 #include "../common.hpp"
 #include "../../../include/omx/program_resample.h"
+#include "program_carried.hpp"
 
 namespace omx {
 
@@ -18,9 +19,6 @@ constexpr uint32_t kRsThreads = 256;          // threads per workgroup of the ma
 // tile of a plan is the longest (at most kRsThreads) whose reach, (tile - 1) * M / L + 1 + T frames, fits: 256 for every common pair
 // (44.1 -> 48 kHz reaches 299 frames, 96 -> 48 kHz 639), 16 at the far end (L = 1, M = 64, T = 1024).
 constexpr uint32_t kRsStageFrames = 2048;
-
-constexpr uint32_t kRsFlagClear = 1u;  // the record is cleared before anything else (a reset)
-constexpr uint32_t kRsFlagFlush = 2u;  // x = 0 at and beyond the last frame taken; the stream is flushed afterwards
 
 // What one call does to one stream: made on the host (which mirrors N, E and the flushed flag), uploaded per call.
 struct RsStreamCall {
@@ -31,7 +29,7 @@ struct RsStreamCall {
     uint32_t frames;    // F: frames taken in this call
     uint32_t emit;      // E' - E: frames written to d_out[s]
     uint32_t ring;      // n_old mod (T - 1): the ring's slot of frame n_old
-    uint32_t flags;     // kRsFlag*
+    uint32_t flags;     // kCarryFlag*
     uint32_t _pad;
 };
 
@@ -68,11 +66,7 @@ struct ProgramResampler {
     omx_program_resample_rule rule{};
     omx_program_resample_info info{};
     uint32_t channels = 0;
-    struct Mirror {
-        uint64_t n = 0, e = 0;
-        bool flushed = false;
-    };
-    std::vector<Mirror> h_streams;
+    std::vector<CarryLedger> h_streams;
     std::vector<RsStreamCall> h_calls;
     DeviceBuffer<RsStreamCall> calls;
     DeviceBuffer<omx_program_resample_record> records;

@@ -31,15 +31,6 @@ namespace {
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ float rs_x_at(const RsArgs& a, const RsStreamCall& call, uint32_t s, int64_t rel, uint32_t c) {
-    if ((int64_t)call.n_old + rel < 0 || rel >= (int64_t)call.frames) return 0.0f;
-    if (rel >= 0) return a.in[((uint64_t)s * a.frames_capacity + (uint64_t)rel) * a.channels + c];
-    if (rel < -(int64_t)a.history) return 0.0f;  // (no emitted frame reaches further back than T - 1 frames: the header's STREAMING)
-    int64_t slot = (int64_t)call.ring + rel;
-    if (slot < 0) slot += a.history;
-    return a.ring[((uint64_t)s * a.history + (uint64_t)slot) * a.channels + c];
-}
-
 __device__ __forceinline__ omx_program_resample_record rs_idle_record(const RsArgs& a) {
     omx_program_resample_record r{};
     r.out_sample_peak_db = a.floor_db;
@@ -56,13 +47,8 @@ __global__ __launch_bounds__(64) void rs_begin_kernel(RsArgs a, uint32_t whole_c
     if (s >= a.n_streams) return;
     const RsStreamCall c = a.calls[s];
     omx_program_resample_record r = a.records[s];
-    if (c.flags & kRsFlagClear) r = rs_idle_record(a);
-    if (whole_call) {
-        r.frames_in = c.n_old + c.frames;
-        r.frames_out = c.e_old + c.emit;
-        r.frames_written = c.emit;
-        r.state = (c.flags & kRsFlagFlush) ? OMX_RESAMPLE_FLUSHED : (r.frames_in != 0 ? OMX_RESAMPLE_RUNNING : OMX_RESAMPLE_IDLE);
-    }
+    if (c.flags & kCarryFlagClear) r = rs_idle_record(a);
+    if (whole_call) ps_begin_record<OMX_RESAMPLE_IDLE, OMX_RESAMPLE_RUNNING, OMX_RESAMPLE_FLUSHED>(r, c.n_old, c.e_old, c.frames, c.emit, c.flags);
     a.records[s] = r;
 }
 
@@ -158,7 +144,8 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
             }
         }
     } else {
-        for (uint32_t idx = tid; idx < n; idx += kRsThreads) stage(idx, rs_x_at(a, call, s, rel_base + (int64_t)(idx / C), idx % C));
+        // (no emitted frame reaches further back than the ring's T - 1 frames: the header's STREAMING)
+        for (uint32_t idx = tid; idx < n; idx += kRsThreads) stage(idx, ps_ring_x_at(a, call, s, rel_base + (int64_t)(idx / C), idx % C));
     }
     __syncthreads();
 
@@ -212,31 +199,25 @@ __global__ __launch_bounds__(kRsThreads) void rs_main_kernel(RsArgs a, uint32_t 
 __global__ __launch_bounds__(256) void rs_carry_kernel(RsArgs a, uint32_t s_base) {
     const uint32_t s = s_base + blockIdx.y;
     const RsStreamCall call = a.calls[s];
-    const uint32_t C = a.channels, e = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t nx = min(call.frames, a.history);
-    if (e < nx * C) {
-        const uint32_t fr = e / C, c = e - fr * C;
-        const uint64_t rel = (uint64_t)(call.frames - nx) + fr;
-        const uint64_t slot = ((uint64_t)call.ring + rel) % a.history;
-        a.ring[((uint64_t)s * a.history + slot) * C + c] = a.in[((uint64_t)s * a.frames_capacity + rel) * C + c];
-    }
+    const uint32_t C = a.channels;
+    ps_carry_row(a.ring + (uint64_t)s * a.history * C, a.history, C, call.ring, call.frames, blockIdx.x * 256 + threadIdx.x,
+                 [&](uint64_t rel, uint32_t c) { return a.in[((uint64_t)s * a.frames_capacity + rel) * C + c]; });
 }
-
-constexpr uint32_t kRsSlab = 65535;  // streams per launch: the y extent of a grid
 
 template <int C>
 void rs_launch_main(const RsArgs& a, uint32_t tiles, size_t lds, hipStream_t stream) {
-    for (uint32_t s0 = 0; s0 < a.n_streams; s0 += kRsSlab)
-        hipLaunchKernelGGL(rs_main_kernel<C>, dim3(tiles, std::min(kRsSlab, a.n_streams - s0)), dim3(kRsThreads), lds, stream, a, s0);
+    for_stream_slabs(a.n_streams, tiles, [&](uint32_t base, uint32_t count) {
+        hipLaunchKernelGGL(rs_main_kernel<C>, dim3(tiles, count), dim3(kRsThreads), lds, stream, a, base);
+    });
 }
 
 }  // namespace
 
 void launch_rs_begin(const RsArgs& a, bool whole_call, hipStream_t stream) {
-    hipLaunchKernelGGL(rs_begin_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a, whole_call ? 1u : 0u);
+    ps_launch_per_stream(rs_begin_kernel, a.n_streams, stream, a, whole_call ? 1u : 0u);
 }
 void launch_rs_finish(const RsArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(rs_finish_kernel, dim3((a.n_streams + 63) / 64), dim3(64), 0, stream, a);
+    ps_launch_per_stream(rs_finish_kernel, a.n_streams, stream, a);
 }
 void launch_rs_main(const RsArgs& a, hipStream_t stream) {
     const uint32_t tiles = (uint32_t)(((uint64_t)a.max_emit + a.tile - 1) / a.tile);
@@ -254,8 +235,9 @@ void launch_rs_main(const RsArgs& a, hipStream_t stream) {
 }
 void launch_rs_carry(const RsArgs& a, hipStream_t stream) {
     const uint32_t tiles = (a.history * a.channels + 255) / 256;
-    for (uint32_t s0 = 0; s0 < a.n_streams; s0 += kRsSlab)
-        hipLaunchKernelGGL(rs_carry_kernel, dim3(tiles, std::min(kRsSlab, a.n_streams - s0)), dim3(256), 0, stream, a, s0);
+    for_stream_slabs(a.n_streams, tiles, [&](uint32_t base, uint32_t count) {
+        hipLaunchKernelGGL(rs_carry_kernel, dim3(tiles, count), dim3(256), 0, stream, a, base);
+    });
 }
 
 }  // namespace omx

@@ -1,8 +1,10 @@
 // What the kernels of the programme bank's stages share: the dB figure of a power, the distance to the next 16-byte boundary, the
 // folds of a per-thread value over a wavefront and a workgroup, the tally of a pass's output (samples over full scale, sample peak)
-// with its commit to the stream's record, and the launch loop over slabs of streams.  Include from .hip files only.
+// with its commit to the stream's record, the ring read, the carry and the record begin of the stages that carry state between calls,
+// the launch of a per-stream kernel and the launch loop over slabs of streams.  Include from .hip files only.
 #pragma once
 #include "../common.hpp"
+#include "program_carried.hpp"
 
 namespace omx {
 
@@ -92,6 +94,52 @@ struct PsTally {
         if (peak > 0.0f) atomicMax(reinterpret_cast<unsigned int*>(&r->out_sample_peak), __float_as_uint(peak));
     }
 };
+
+// ---- what the stages that carry state between calls share (program_carried.hpp holds the host's half).  `rel` counts a stream's
+// frames from the first frame of the call; a ring of `length` entries holds entry n of the stream at slot n mod length, and a call's
+// table hands over `ring`, the slot of the call's first entry.
+
+// Sample (frame rel, channel c) of stream s for a stage whose ring holds the `history` frames in front of the call: +0 in front of the
+// stream, at and beyond the last frame taken (which only a flush reads) and further back than the ring reaches (which nothing the stage
+// emits reads), the call's PCM at rel >= 0, the ring below.  Args: in, frames_capacity, channels, history, ring; Call: n_old, frames, ring.
+template <class Args, class Call>
+__device__ __forceinline__ float ps_ring_x_at(const Args& a, const Call& call, uint32_t s, int64_t rel, uint32_t c) {
+    if ((int64_t)call.n_old + rel < 0 || rel >= (int64_t)call.frames) return 0.0f;
+    if (rel >= 0) return a.in[((uint64_t)s * a.frames_capacity + (uint64_t)rel) * a.channels + c];
+    if (rel < -(int64_t)a.history) return 0.0f;
+    int64_t slot = (int64_t)call.ring + rel;
+    if (slot < 0) slot += a.history;
+    return a.ring[((uint64_t)s * a.history + (uint64_t)slot) * a.channels + c];
+}
+
+// A row into its ring, for thread e of the carry pass: element e of the newest min(frames, length) entries of the call's row (entries of
+// `width` elements; fetch(rel, c) is element c of entry rel) goes to slot (ring + rel) mod length of `row`, the stream's ring.  The slots
+// it does not write keep the older entries, so a call of fewer entries than the ring holds, or of none, leaves the newest `length` in place.
+template <class T, class Fetch>
+__device__ __forceinline__ void ps_carry_row(T* row, uint32_t length, uint32_t width, uint32_t ring, uint32_t frames, uint32_t e, Fetch&& fetch) {
+    const uint32_t nx = min(frames, length);
+    if (e < nx * width) {  // (never with length 0)
+        const uint32_t fr = e / width, c = e - fr * width;
+        const uint64_t rel = (uint64_t)(frames - nx) + fr;
+        const uint64_t slot = ((uint64_t)ring + rel) % length;
+        row[slot * width + c] = fetch(rel, c);
+    }
+}
+
+// What a begin kernel writes of a whole call into the stream's record: the counters behind the call and the state
+template <uint32_t IDLE, uint32_t RUNNING, uint32_t FLUSHED, class Record>
+__device__ __forceinline__ void ps_begin_record(Record& r, uint64_t n_old, uint64_t e_old, uint32_t frames, uint32_t emit, uint32_t flags) {
+    r.frames_in = n_old + frames;
+    r.frames_out = e_old + emit;
+    r.frames_written = emit;
+    r.state = (flags & kCarryFlagFlush) ? FLUSHED : (r.frames_in != 0 ? RUNNING : IDLE);
+}
+
+// ---- launch of a kernel with one thread per stream (the begin and finish kernels): workgroups of 64
+template <class... Params, class... Args>
+void ps_launch_per_stream(void (*kernel)(Params...), uint32_t n_streams, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((n_streams + 63) / 64), dim3(64), 0, stream, args...);
+}
 
 // ---- launches of a (tiles, streams) grid.  A launch holds at most 65535 streams in y and fewer than 2^32 threads (workgroups of up
 // to 256): launch(base, count) once per slab of streams.
